@@ -7,7 +7,12 @@ photon of this rank's shard, RCCL-reduce the per-GPU lightmaps to rank 0 (N > 1)
 texels on rank 0. Host<->device copies of the geometry and texels are outside the timed region.
 
   python bench.py [--gpus N --steps K --warmup W --config box200|box2000|example|box200-1e10]
+                  [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds the CPU legs
+(cpu_baseline*: the reference's algorithm and its own CPU paths timed on the host, ~10 s each).
+--dump-outputs DIR writes what the last timed step left its caller, as DIR/<name>.npy (dump_outputs).
 
 Default (N=1): BASELINE config 3 -- synthetic 200-rectangle box, spa=172,413,793 = 1,000,012,800
 photons per step. Multi-GPU is weak scaling: spa x N photons per step, sharded evenly by work item.
@@ -285,6 +290,18 @@ def binding_of(issue, atomic_rate):
                        % (100 * w["waiting"], 100 * w["issuing"], 100 * fr["valu"], 100 * fr["vmem"]))
 
 
+def dump_outputs(d, lm, tex_out):
+    """What a caller of the timed path holds after its last step, as float64 / float32 .npy files:
+      lightmap.npy  (texels, 4) float64: the int64 fixed-point RGB sums of the bake (and the RCCL reduce),
+                    exact while |sum| < 2^53
+      texels.npy    (texels, 4) float32: the finalised texels (fmgi_finalize's output)
+    The schedule comes from srand(1) and the scene generator, and the bake sums integers, so two runs with
+    the same arguments write the same bytes."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "lightmap.npy"), lm.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "texels.npy"), tex_out.cpu().numpy().astype(np.float32))
+
+
 def weak_spa(cfg, world):
     """numSamplesPerArea of a step on `world` GPUs: weak configs take spa x world (the reference's int
     argument, global_illumination_cl.h:10), clamped to INT_MAX; the photons actually planned are what the
@@ -302,7 +319,11 @@ def main():
     ap.add_argument("--kernel", default="auto", choices=["auto", "grid", "fast", "exact", "hybrid"])
     ap.add_argument("--accum", default="auto", choices=["auto", "fx3", "state", "stream", "none"],
                     help="none = PROFILING ONLY (deposits discarded; lightmap wrong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU legs (cpu_baseline*) on the host after the GPU steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--spa", type=int, default=0, help="override numSamplesPerArea of the config (per GPU)")
     args = ap.parse_args()
@@ -449,6 +470,8 @@ def main():
     else:
         scans, deposits, photons_done = float(st["scans"]), float(st["deposits"]), float(st["photons"])
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lm, tex_out)
     if rank == 0:
         assert int(photons_done) == photons_per_step * args.steps, (photons_done, photons_per_step)
         value = photons_per_step * args.steps / elapsed
@@ -586,7 +609,7 @@ def main():
             ctx.lib.fmgi_get_stage_cycles(ctx.h, cyc)
             out["in_kernel_clock_ghz"] = 0.1 * cyc[8] / max(cyc[9], 1)
             out["note"] = "CLOCK BUILD (FMGI_CLOCK_STAMP): in-kernel clock of k_bake, median-free wave-time weighted"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the reference kernel's algorithm on every host thread (the CL_DEVICE_TYPE_CPU analogue; the
             # reference photonmap.cl itself cannot be built for the host here: DESIGN.md §5)
             out["cpu_baseline"] = cpu_baseline(sc, cfg["spa"], args.cpu_seconds)
