@@ -26,6 +26,7 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_rad.h"
+#include "fmgi_view.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
 
@@ -138,19 +139,6 @@ int num_mip_texels(const int32_t *lm) { /* rectangle.c:166-190 (asserts compiled
     return n;
 }
 
-AoRect hit_rect(const fmgi_rect &r) { /* intersects()'s per-call values, rectangle.c:67-95 */
-    AoRect a;
-    memset(&a, 0, sizeof a);
-    a.nx = r.n.s[0], a.ny = r.n.s[1], a.nz = r.n.s[2];
-    a.px = r.pos.s[0], a.py = r.pos.s[1], a.pz = r.pos.s[2];
-    const F3 w = f3of(r.width), h = f3of(r.height);
-    const float wl = length(w), hl = length(h);
-    const F3 wn = div_vec3(w, wl), hn = div_vec3(h, hl);
-    a.wx = wn.x, a.wy = wn.y, a.wz = wn.z, a.wl = wl;
-    a.hx = hn.x, a.hy = hn.y, a.hz = hn.z, a.hl = hl;
-    return a;
-}
-
 fmgi_rad_stats g_stats;
 
 #define RADCHK(expr)                                                                                   \
@@ -227,13 +215,8 @@ int rad_run(const fmgi_geometry *geo, fmgi_vec3 *texels_out, int32_t *sids_out) 
     std::vector<AoRect> hits((size_t)std::max(nr, 1));
     for (int i = 0; i < nr; i++) {
         const fmgi_rect &r = all[(size_t)i];
-        RadRect &o = rects[(size_t)i];
-        o.px = r.pos.s[0], o.py = r.pos.s[1], o.pz = r.pos.s[2];
-        o.wx = r.width.s[0], o.wy = r.width.s[1], o.wz = r.width.s[2];
-        o.hx = r.height.s[0], o.hy = r.height.s[1], o.hz = r.height.s[2];
-        o.nx = r.n.s[0], o.ny = r.n.s[1], o.nz = r.n.s[2];
-        o.s0 = r.lightmapSetup[0], o.s1 = r.lightmapSetup[1], o.s2 = r.lightmapSetup[2], o.pad = 0;
-        hits[(size_t)i] = hit_rect(r);
+        rects[(size_t)i] = fmgi_rad_rect(r);
+        hits[(size_t)i] = fmgi_rad_hit_rect(r);
     }
     int sort_n = 2;
     while (sort_n < nr) sort_n <<= 1;
@@ -426,6 +409,30 @@ done:
 }
 
 } // namespace
+
+/* the two device images of a rectangle; the view renderer uploads its walls as the same (fmgi_view.h) */
+AoRect fmgi_rad_hit_rect(const fmgi_rect &r) { /* intersects()'s per-call values, rectangle.c:67-95 */
+    AoRect a;
+    memset(&a, 0, sizeof a);
+    a.nx = r.n.s[0], a.ny = r.n.s[1], a.nz = r.n.s[2];
+    a.px = r.pos.s[0], a.py = r.pos.s[1], a.pz = r.pos.s[2];
+    const F3 w = f3of(r.width), h = f3of(r.height);
+    const float wl = length(w), hl = length(h);
+    const F3 wn = div_vec3(w, wl), hn = div_vec3(h, hl);
+    a.wx = wn.x, a.wy = wn.y, a.wz = wn.z, a.wl = wl;
+    a.hx = hn.x, a.hy = hn.y, a.hz = hn.z, a.hl = hl;
+    return a;
+}
+
+RadRect fmgi_rad_rect(const fmgi_rect &r) { /* the candidate tests' values, rectangle.c:97-113, :442-470 */
+    RadRect o;
+    o.px = r.pos.s[0], o.py = r.pos.s[1], o.pz = r.pos.s[2];
+    o.wx = r.width.s[0], o.wy = r.width.s[1], o.wz = r.width.s[2];
+    o.hx = r.height.s[0], o.hy = r.height.s[1], o.hz = r.height.s[2];
+    o.nx = r.n.s[0], o.ny = r.n.s[1], o.nz = r.n.s[2];
+    o.s0 = r.lightmapSetup[0], o.s1 = r.lightmapSetup[1], o.s2 = r.lightmapSetup[2], o.pad = 0;
+    return o;
+}
 
 FMGI_API int fmgi_radiosity(const fmgi_geometry *geo, fmgi_vec3 *texels_out, int32_t *sids_out) {
     return rad_run(geo, texels_out, sids_out);

@@ -1,7 +1,8 @@
 /*
  * fmgi_rect_dev.h -- device-side fp32 vector helpers and the ray/rectangle test of the native C
- * backends (vector3_cl.c, rectangle.c:67-95 intersects), shared by the ambient-occlusion (fmgi_ao.hip)
- * and radiosity (fmgi_rad.hip) kernels. Every operation is IEEE fp32 in the reference's source order;
+ * backends (vector3_cl.c, rectangle.c:67-95 intersects), shared by the ambient-occlusion (fmgi_ao.hip),
+ * radiosity (fmgi_rad.hip) and view (fmgi_view.hip) kernels; the candidate-list helpers (isBehindRay,
+ * getShortestDistanceRectToPoint, the x86 cast) serve the last two. Every operation is IEEE fp32 in the reference's source order;
  * the including file turns contraction off (#pragma clang fp contract(off)) before including this.
  */
 #ifndef FMGI_RECT_DEV_H
@@ -38,6 +39,34 @@ __device__ __forceinline__ float rect_intersects(const AoRect &r, v3 src, v3 dir
     if (dx < 0 || dy < 0 || dx > r.wl || dy > r.hl) return -1;
     return fac;
 }
+
+/* rectangle.c:97-113 isBehindRay */
+__device__ __forceinline__ bool behind_ray(v3 p, v3 w, v3 h, v3 src, v3 dir) {
+    const v3 d1 = sub(p, src), d2 = sub(add(p, w), src), d3 = sub(add(p, h), src), d4 = sub(add(add(p, w), h), src);
+    return dot(d1, dir) < 0 && dot(d2, dir) < 0 && dot(d3, dir) < 0 && dot(d4, dir) < 0;
+}
+
+__device__ __forceinline__ float len3(v3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
+__device__ __forceinline__ v3 unit(v3 a) { return mul(a, 1.0f / len3(a)); }
+
+/* rectangle.c:442-470 getShortestDistanceRectToPoint */
+__device__ __forceinline__ float min_dist(v3 pos, v3 w, v3 h, v3 n, v3 p) {
+    const v3 vd = sub(p, pos);
+    const v3 on_plane = sub(p, mul(n, dot(vd, n)));
+    const v3 pd = sub(on_plane, pos);
+    float u = dot(pd, unit(h)) / len3(h);
+    float v = dot(pd, unit(w)) / len3(w);
+    u = (u < 0) ? 0.0f : ((u > 1) ? 1.0f : u);
+    v = (v < 0) ? 0.0f : ((v > 1) ? 1.0f : v);
+    return len3(sub(p, add(add(pos, mul(w, v)), mul(h, u))));
+}
+
+/* x86-64 cvttss2si, the reference's (int) cast: out of range and NaN give INT_MIN */
+__device__ __forceinline__ int cvt_x86(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 } // namespace fmgi_dev
 

@@ -1,0 +1,70 @@
+/*
+ * fmgi_view.h -- shared host/device structures of the view renderer: the reference's debug raycaster
+ * (debugRaytracer.cc:121-176) on the GPU, for any pin-hole camera and for batches of cameras.
+ *
+ * The reference builds one sorted candidate list per camera (getSortedIntersectableRects,
+ * radiosityNative.c:25-62, over the walls only) and casts one ray per pixel through
+ * findClosestIntersectionSorted (radiosityNative.c:67-90). Here:
+ *   k_view_candidates  one workgroup per camera: k_rad_rays's prologue (backface / isBehindRay culling,
+ *                      getShortestDistanceRectToPoint keys, bitonic sort on (distance, index)) written to a
+ *                      global [cameras][sort_n] key array and a per-camera count;
+ *   k_view_rays        one lane per pixel, one wave per 8x8 pixel block: the screen position and ray of
+ *                      debugRaytracer.cc:154-155, the sorted walk with its early exit, getTileIdAt
+ *                      (rectangle.c:205-230) at the hit point, and the RGB8 bytes of the hit tile.
+ * The rectangles are the radiosity backend's RadRect / AoRect images of the walls, built by the same host
+ * code (fmgi_rad_host.cpp), so edge lengths and unit edges carry the same bits in both backends.
+ */
+#ifndef FMGI_VIEW_H
+#define FMGI_VIEW_H
+
+#include <stdint.h>
+
+#include <hip/hip_runtime_api.h>
+
+#include "fmgi_rad.h"
+
+#define FMGI_VIEW_TILE 8   /* a wave covers TILE x TILE pixels */
+#define FMGI_VIEW_BLOCK 16 /* a workgroup of 256 lanes covers BLOCK x BLOCK pixels (2 x 2 waves) */
+#define FMGI_VIEW_MAX_DIM (65535 * FMGI_VIEW_BLOCK) /* grid limit of the pixel-tile axes */
+#define FMGI_VIEW_MAX_BATCH 65535                   /* cameras per launch (grid z) */
+
+/* one camera, set up on the host in fp32 (debugRaytracer.cc:121-125) */
+struct ViewCam {
+    float px, py, pz; /* camPos */
+    float dx, dy, dz; /* camDir = normalized(dir) */
+    float cx, cy, cz; /* screenCenter = camPos + camDir */
+    float rx, ry, rz; /* camRight = cross(camDir, up) */
+    float ux, uy, uz; /* up, as given */
+    float pixel;      /* the reference's dx = dy */
+};
+static_assert(sizeof(ViewCam) == 64, "ViewCam must be 64 B");
+
+struct ViewArgs {
+    const RadRect *rects; /* the walls */
+    const AoRect *hits;   /* the same walls as intersects() sees them */
+    int nrects;
+    int sort_n;           /* power of two >= nrects */
+    const ViewCam *cams;  /* this launch's cameras */
+    int ncams;
+    int width, height;
+    unsigned long long *keys; /* [ncams][sort_n]: (minDistance bits << 32) | wall index, ~0 for culled walls */
+    int32_t *counts;          /* [ncams] */
+    const int64_t *first_tile; /* [nrects]: running sum of s1 * s2 (null without tiles) */
+    const uint8_t *tiles_rgb;  /* the output step's RGB8 tiles in wall order (null: no rgb) */
+    uint32_t background;       /* r | g << 8 | b << 16 */
+    int32_t *wall_out;         /* [ncams][height][width] each, or null */
+    int32_t *texel_out;
+    float *dist_out;
+    uint8_t *rgb_out;          /* [ncams][height][width][3], or null */
+    unsigned long long *tests; /* one counter: intersects() evaluations */
+};
+
+hipError_t fmgi_view_launch_candidates(const ViewArgs &a, hipStream_t s);
+hipError_t fmgi_view_launch_rays(const ViewArgs &a, hipStream_t s);
+
+/* the radiosity backend's host images of a rectangle (fmgi_rad_host.cpp) */
+struct fmgi_rect;
+RadRect fmgi_rad_rect(const fmgi_rect &r);
+AoRect fmgi_rad_hit_rect(const fmgi_rect &r);
+
+#endif

@@ -1,0 +1,306 @@
+/*
+ * fmgi_view_host.cpp -- host side of the view renderer and its C ABI (include/flatmatch_gi.h:
+ * fmgi_render_views, fmgi_view_candidates, fmgi_view_stats). The reference is the debug raycaster
+ * (debugRaytracer.cc:121-176) over getSortedIntersectableRects / findClosestIntersectionSorted
+ * (radiosityNative.c:25-90).
+ *
+ * The host checks every argument before the first device call, sets each camera up in fp32 in the
+ * reference's order (built with -ffp-contract=off, no FMA), uploads the walls as the radiosity backend's
+ * RadRect / AoRect images, runs the two kernels (fmgi_view.hip) over chunks of cameras and copies the
+ * requested outputs back.
+ */
+#include <hip/hip_runtime_api.h>
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/flatmatch_gi.h"
+#include "fmgi_view.h"
+
+#define FMGI_API extern "C" __attribute__((visibility("default")))
+
+int internal_set_err(int code, const char *msg);
+
+namespace {
+
+struct F3 {
+    float x, y, z;
+};
+F3 add(F3 a, F3 b) { return F3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+F3 mul(F3 a, float f) { return F3{a.x * f, a.y * f, a.z * f}; }
+F3 cross(F3 a, F3 b) { return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+float length(F3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
+F3 normalized(F3 a) { return mul(a, 1.0f / length(a)); } /* vector3_cl.c:95-101 */
+
+struct fmgi_view_stats g_stats;
+
+#define VIEWCHK(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            char b_[256];                                                                              \
+            snprintf(b_, sizeof b_, "%s: %s", #expr, hipGetErrorString(e_));                           \
+            rc = internal_set_err(e_ == hipErrorOutOfMemory ? FMGI_ERR_OOM : FMGI_ERR_HIP, b_);        \
+            goto done;                                                                                 \
+        }                                                                                              \
+    } while (0)
+
+/* the walls as both backends' device images, and the tiles' running sum */
+struct Walls {
+    std::vector<RadRect> rects;
+    std::vector<AoRect> hits;
+    std::vector<int64_t> first_tile;
+    int sort_n = 2;
+};
+
+int check_geometry(const fmgi_geometry *geo, Walls &w) {
+    if (!geo) return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: null geometry");
+    if (geo->numWalls < 0 || geo->numTexels < 0 || (geo->numWalls && !geo->walls))
+        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: bad geometry");
+    if (geo->numWalls > FMGI_RAD_MAX_SORT)
+        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: more walls than the candidate sort holds (16384)");
+    const int nr = geo->numWalls;
+    w.rects.resize((size_t)std::max(nr, 1));
+    w.hits.resize((size_t)std::max(nr, 1));
+    w.first_tile.resize((size_t)std::max(nr, 1));
+    int64_t tiles = 0;
+    for (int i = 0; i < nr; i++) {
+        const fmgi_rect &r = geo->walls[i];
+        const int32_t *lm = r.lightmapSetup;
+        if (lm[1] < 1 || lm[2] < 1 || lm[0] < 0 || (int64_t)lm[1] * lm[2] > (1 << 28) ||
+            (int64_t)lm[0] + (int64_t)lm[1] * lm[2] > geo->numTexels)
+            return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a wall's texels lie outside numTexels");
+        w.rects[(size_t)i] = fmgi_rad_rect(r);
+        w.hits[(size_t)i] = fmgi_rad_hit_rect(r);
+        w.first_tile[(size_t)i] = tiles;
+        tiles += (int64_t)lm[1] * lm[2];
+    }
+    while (w.sort_n < nr) w.sort_n <<= 1;
+    return FMGI_OK;
+}
+
+/* debugRaytracer.cc:121-125 */
+int make_cam(const fmgi_camera &c, ViewCam &o) {
+    if (!(c.pixel > 0) || !isfinite(c.pixel))
+        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a camera's pixel size is not finite and positive");
+    const F3 pos{c.pos[0], c.pos[1], c.pos[2]}, d{c.dir[0], c.dir[1], c.dir[2]}, up{c.up[0], c.up[1], c.up[2]};
+    const float len = length(d);
+    if (!(len > 0) || !isfinite(len))
+        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a camera's direction has no length");
+    const F3 dir = normalized(d);
+    const F3 centre = add(pos, dir);
+    const F3 right = cross(dir, up);
+    o.px = pos.x, o.py = pos.y, o.pz = pos.z;
+    o.dx = dir.x, o.dy = dir.y, o.dz = dir.z;
+    o.cx = centre.x, o.cy = centre.y, o.cz = centre.z;
+    o.rx = right.x, o.ry = right.y, o.rz = right.z;
+    o.ux = up.x, o.uy = up.y, o.uz = up.z;
+    o.pixel = c.pixel;
+    return FMGI_OK;
+}
+
+int no_device() {
+    int dev_count = 0;
+    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0)
+        return internal_set_err(FMGI_ERR_NO_DEVICE, "no HIP device visible");
+    return FMGI_OK;
+}
+
+int view_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+             const uint8_t *tiles_rgb, const uint8_t *background, int32_t *wall_out, int32_t *texel_out,
+             float *dist_out, uint8_t *rgb_out) {
+    Walls w;
+    int rc = check_geometry(geo, w);
+    if (rc != FMGI_OK) return rc;
+    if (width < 1 || height < 1 || width > FMGI_VIEW_MAX_DIM || height > FMGI_VIEW_MAX_DIM)
+        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: bad image size");
+    if (num_cams < 0 || (num_cams && !cams)) return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: bad cameras");
+    if (rgb_out && !tiles_rgb) return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: rgb_out needs tiles_rgb");
+    std::vector<ViewCam> vc((size_t)std::max(num_cams, 1));
+    for (int i = 0; i < num_cams; i++)
+        if ((rc = make_cam(cams[i], vc[(size_t)i])) != FMGI_OK) return rc;
+    memset(&g_stats, 0, sizeof g_stats);
+    if (num_cams == 0) return FMGI_OK;
+    if ((rc = no_device()) != FMGI_OK) return rc;
+
+    const int nr = geo->numWalls;
+    const int64_t pix = (int64_t)width * height;
+    /* cameras per launch: at most 2^26 pixels of outputs on the device at a time */
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)num_cams, FMGI_VIEW_MAX_BATCH, ((int64_t)1 << 26) / pix}));
+    const int64_t tile_bytes = 3 * (w.first_tile[(size_t)std::max(nr, 1) - 1] +
+                                    (nr ? (int64_t)geo->walls[nr - 1].lightmapSetup[1] * geo->walls[nr - 1].lightmapSetup[2] : 0));
+    RadRect *d_rects = nullptr;
+    AoRect *d_hits = nullptr;
+    ViewCam *d_cams = nullptr;
+    unsigned long long *d_keys = nullptr, *d_tests = nullptr;
+    int32_t *d_counts = nullptr, *d_wall = nullptr, *d_texel = nullptr;
+    int64_t *d_first = nullptr;
+    uint8_t *d_tiles = nullptr, *d_rgb = nullptr;
+    float *d_dist = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<int32_t> counts((size_t)batch);
+    unsigned long long tests = 0;
+    ViewArgs a;
+    memset(&a, 0, sizeof a);
+    {
+        const char *dv = getenv("FMGI_DEVICE");
+        VIEWCHK(hipSetDevice(dv ? atoi(dv) : 0));
+    }
+    for (auto &e : ev) VIEWCHK(hipEventCreate(&e));
+    VIEWCHK(hipEventRecord(ev[0], nullptr));
+    VIEWCHK(hipMalloc(&d_rects, w.rects.size() * sizeof(RadRect)));
+    VIEWCHK(hipMemcpy(d_rects, w.rects.data(), w.rects.size() * sizeof(RadRect), hipMemcpyHostToDevice));
+    VIEWCHK(hipMalloc(&d_hits, w.hits.size() * sizeof(AoRect)));
+    VIEWCHK(hipMemcpy(d_hits, w.hits.data(), w.hits.size() * sizeof(AoRect), hipMemcpyHostToDevice));
+    VIEWCHK(hipMalloc(&d_cams, (size_t)batch * sizeof(ViewCam)));
+    VIEWCHK(hipMalloc(&d_keys, (size_t)batch * w.sort_n * 8));
+    VIEWCHK(hipMalloc(&d_counts, (size_t)batch * 4));
+    VIEWCHK(hipMalloc(&d_tests, 8));
+    VIEWCHK(hipMemset(d_tests, 0, 8));
+    if (wall_out) VIEWCHK(hipMalloc(&d_wall, (size_t)batch * pix * 4));
+    if (texel_out) VIEWCHK(hipMalloc(&d_texel, (size_t)batch * pix * 4));
+    if (dist_out) VIEWCHK(hipMalloc(&d_dist, (size_t)batch * pix * 4));
+    if (rgb_out) {
+        VIEWCHK(hipMalloc(&d_rgb, (size_t)batch * pix * 3));
+        VIEWCHK(hipMalloc(&d_first, w.first_tile.size() * 8));
+        VIEWCHK(hipMemcpy(d_first, w.first_tile.data(), w.first_tile.size() * 8, hipMemcpyHostToDevice));
+        VIEWCHK(hipMalloc(&d_tiles, (size_t)std::max<int64_t>(tile_bytes, 1)));
+        if (tile_bytes) VIEWCHK(hipMemcpy(d_tiles, tiles_rgb, (size_t)tile_bytes, hipMemcpyHostToDevice));
+    }
+    a.rects = d_rects;
+    a.hits = d_hits;
+    a.nrects = nr;
+    a.sort_n = w.sort_n;
+    a.cams = d_cams;
+    a.width = width;
+    a.height = height;
+    a.keys = d_keys;
+    a.counts = d_counts;
+    a.first_tile = d_first;
+    a.tiles_rgb = d_tiles;
+    a.background = background ? ((uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16)) : 0;
+    a.wall_out = d_wall;
+    a.texel_out = d_texel;
+    a.dist_out = d_dist;
+    a.rgb_out = d_rgb;
+    a.tests = d_tests;
+    for (int c0 = 0; c0 < num_cams; c0 += batch) {
+        const int n = std::min(batch, num_cams - c0);
+        const size_t px = (size_t)n * pix, o = (size_t)c0 * pix;
+        a.ncams = n;
+        VIEWCHK(hipMemcpy(d_cams, vc.data() + c0, (size_t)n * sizeof(ViewCam), hipMemcpyHostToDevice));
+        VIEWCHK(hipEventRecord(ev[1], nullptr));
+        VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+        VIEWCHK(hipEventRecord(ev[2], nullptr));
+        VIEWCHK(fmgi_view_launch_rays(a, nullptr));
+        VIEWCHK(hipEventRecord(ev[3], nullptr));
+        VIEWCHK(hipEventSynchronize(ev[3]));
+        float ms = 0;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+        g_stats.cand_ms += ms;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        g_stats.rays_ms += ms;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[0], ev[3]));
+        g_stats.total_ms = ms;
+        VIEWCHK(hipMemcpy(counts.data(), d_counts, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) g_stats.candidates += counts[(size_t)i];
+        if (wall_out) VIEWCHK(hipMemcpy(wall_out + o, d_wall, px * 4, hipMemcpyDeviceToHost));
+        if (texel_out) VIEWCHK(hipMemcpy(texel_out + o, d_texel, px * 4, hipMemcpyDeviceToHost));
+        if (dist_out) VIEWCHK(hipMemcpy(dist_out + o, d_dist, px * 4, hipMemcpyDeviceToHost));
+        if (rgb_out) VIEWCHK(hipMemcpy(rgb_out + 3 * o, d_rgb, px * 3, hipMemcpyDeviceToHost));
+    }
+    VIEWCHK(hipMemcpy(&tests, d_tests, 8, hipMemcpyDeviceToHost));
+    g_stats.cameras = num_cams;
+    g_stats.rays = (int64_t)num_cams * pix;
+    g_stats.tests = (int64_t)tests;
+done:
+    for (auto &e : ev)
+        if (e) hipEventDestroy(e);
+    hipFree(d_rects);
+    hipFree(d_hits);
+    hipFree(d_cams);
+    hipFree(d_keys);
+    hipFree(d_counts);
+    hipFree(d_tests);
+    hipFree(d_wall);
+    hipFree(d_texel);
+    hipFree(d_dist);
+    hipFree(d_rgb);
+    hipFree(d_first);
+    hipFree(d_tiles);
+    return rc;
+}
+
+int candidates_run(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist, int cap) {
+    Walls w;
+    int rc = check_geometry(geo, w);
+    if (rc != FMGI_OK) return rc;
+    if (!cam) return internal_set_err(FMGI_ERR_ARG, "fmgi_view_candidates: null camera");
+    ViewCam vc;
+    if ((rc = make_cam(*cam, vc)) != FMGI_OK) return rc;
+    if ((rc = no_device()) != FMGI_OK) return rc;
+    RadRect *d_rects = nullptr;
+    ViewCam *d_cams = nullptr;
+    unsigned long long *d_keys = nullptr;
+    int32_t *d_counts = nullptr;
+    std::vector<unsigned long long> keys((size_t)w.sort_n);
+    int32_t count = 0;
+    ViewArgs a;
+    memset(&a, 0, sizeof a);
+    {
+        const char *dv = getenv("FMGI_DEVICE");
+        VIEWCHK(hipSetDevice(dv ? atoi(dv) : 0));
+    }
+    VIEWCHK(hipMalloc(&d_rects, w.rects.size() * sizeof(RadRect)));
+    VIEWCHK(hipMemcpy(d_rects, w.rects.data(), w.rects.size() * sizeof(RadRect), hipMemcpyHostToDevice));
+    VIEWCHK(hipMalloc(&d_cams, sizeof(ViewCam)));
+    VIEWCHK(hipMemcpy(d_cams, &vc, sizeof(ViewCam), hipMemcpyHostToDevice));
+    VIEWCHK(hipMalloc(&d_keys, (size_t)w.sort_n * 8));
+    VIEWCHK(hipMalloc(&d_counts, 4));
+    a.rects = d_rects;
+    a.nrects = geo->numWalls;
+    a.sort_n = w.sort_n;
+    a.cams = d_cams;
+    a.ncams = 1;
+    a.keys = d_keys;
+    a.counts = d_counts;
+    VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    VIEWCHK(hipMemcpy(keys.data(), d_keys, keys.size() * 8, hipMemcpyDeviceToHost));
+    VIEWCHK(hipMemcpy(&count, d_counts, 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < std::min(count, std::max(cap, 0)); i++) {
+        const uint32_t bits = (uint32_t)(keys[(size_t)i] >> 32);
+        if (wall_idx) wall_idx[i] = (int32_t)(uint32_t)keys[(size_t)i];
+        if (min_dist) memcpy(&min_dist[i], &bits, 4);
+    }
+    rc = count;
+done:
+    hipFree(d_rects);
+    hipFree(d_cams);
+    hipFree(d_keys);
+    hipFree(d_counts);
+    return rc;
+}
+
+} // namespace
+
+FMGI_API int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                               const uint8_t *tiles_rgb, const uint8_t background[3], int32_t *wall_out,
+                               int32_t *texel_out, float *dist_out, uint8_t *rgb_out) {
+    return view_run(geo, cams, num_cams, width, height, tiles_rgb, background, wall_out, texel_out, dist_out, rgb_out);
+}
+
+FMGI_API int fmgi_view_candidates(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist,
+                                  int cap) {
+    return candidates_run(geo, cam, wall_idx, min_dist, cap);
+}
+
+FMGI_API int fmgi_view_stats(struct fmgi_view_stats *out) {
+    if (!out) return internal_set_err(FMGI_ERR_ARG, "null stats");
+    *out = g_stats;
+    return FMGI_OK;
+}

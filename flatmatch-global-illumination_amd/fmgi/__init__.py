@@ -21,7 +21,7 @@ from . import scene
 
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
-                   check, load)
+                   ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
 LAUNCH_DTYPE = np.dtype(
@@ -54,6 +54,11 @@ __all__ = [
     "EVENT_DTYPE",
     "device_count",
     "host_sincosf",
+    "CAMERA_DTYPE",
+    "camera",
+    "render_views",
+    "view_candidates",
+    "view_stats",
 ]
 
 
@@ -424,3 +429,72 @@ def output_tiles(sc: Scene, texels: np.ndarray, spa: int, tint_extra: int = 0):
     rgb = np.zeros(max(n, 1), np.uint8)
     check(lib.fmgi_output_tiles(C.byref(g), spa, tint_extra, _ptr(out), _ptr(rgb)), "fmgi_output_tiles")
     return out, rgb[:n]
+
+
+# ---- view renderer (include/flatmatch_gi.h) ---------------------------------------
+
+CAMERA_DTYPE = np.dtype([("pos", "<f4", 3), ("dir", "<f4", 3), ("up", "<f4", 3), ("pixel", "<f4")])
+assert CAMERA_DTYPE.itemsize == 40
+
+
+def camera(pos, dir, up=(0, 0, 1), pixel=0.001) -> np.ndarray:
+    """One fmgi_camera record: position, viewing direction (any non-zero length), up vector (used as given)
+    and the size of a pixel on the screen plane at distance 1 (the reference tool's is 1/1000)."""
+    c = np.zeros((), CAMERA_DTYPE)
+    c["pos"], c["dir"], c["up"], c["pixel"] = pos, dir, up, pixel
+    return c
+
+
+def _cameras(cams) -> np.ndarray:
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(cams, CAMERA_DTYPE)))
+
+
+def render_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray | None = None,
+                 background=(0, 0, 0)) -> dict:
+    """The reference's debug raycaster on the GPU (fmgi_render_views): one width x height image per camera.
+    Returns {"wall", "texel" (int32), "dist" (float32)} as [cameras, height, width] arrays (-1, -1, +inf where a
+    ray hits nothing) and, when tiles_rgb (output_tiles' RGB8 bytes) is given, "rgb" (uint8, a trailing [3]):
+    the hit tile's bytes, or `background`."""
+    lib = load()
+    cams = _cameras(cams)
+    n = len(cams)
+    g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+    tiles = None if tiles_rgb is None else np.ascontiguousarray(tiles_rgb, np.uint8)
+    if tiles is not None and len(tiles) != lib.fmgi_output_tile_bytes(C.byref(g)):
+        raise FmgiError(f"tiles_rgb holds {len(tiles)} bytes, the scene's tiles take {lib.fmgi_output_tile_bytes(C.byref(g))}")
+    want_rgb = tiles is not None
+    out = {"wall": np.empty((n, height, width), np.int32), "texel": np.empty((n, height, width), np.int32),
+           "dist": np.empty((n, height, width), np.float32)}
+    if want_rgb:
+        out["rgb"] = np.empty((n, height, width, 3), np.uint8)
+    bg = np.array(background, np.uint8)
+    assert bg.shape == (3,)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731  (empty arrays keep a valid pointer)
+    check(lib.fmgi_render_views(C.byref(g), p(cams), n, width, height, None if tiles is None else p(tiles), p(bg),
+                                p(out["wall"]), p(out["texel"]), p(out["dist"]), p(out["rgb"]) if want_rgb else None),
+          "fmgi_render_views")
+    del keep
+    return out
+
+
+def view_candidates(sc: Scene, cam):
+    """One camera's sorted candidate list from the device (fmgi_view_candidates): (wall indices int32,
+    minDistance float32), in the order the rays walk it."""
+    lib = load()
+    cams = _cameras(cam)
+    assert len(cams) == 1
+    g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+    cap = len(sc.walls)
+    idx = np.zeros(max(cap, 1), np.int32)
+    md = np.zeros(max(cap, 1), np.float32)
+    n = check(lib.fmgi_view_candidates(C.byref(g), cams.ctypes.data_as(C.c_void_p), _ptr(idx), _ptr(md), cap),
+              "fmgi_view_candidates")
+    del keep
+    return idx[:n], md[:n]
+
+
+def view_stats() -> dict:
+    """fmgi_view_stats: the last render_views call's cameras, rays, candidates, intersects() tests and times."""
+    st = ViewStats()
+    check(load().fmgi_view_stats(C.byref(st)), "fmgi_view_stats")
+    return st.as_dict()

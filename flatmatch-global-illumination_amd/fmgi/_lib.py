@@ -65,6 +65,9 @@ EXPORTS = (
     "fmgi_radiosity_jobs",
     "fmgi_radiosity_stats",
     "fmgi_rand_skip",
+    "fmgi_render_views",
+    "fmgi_view_candidates",
+    "fmgi_view_stats",
 )
 
 KERNEL_EXACT = 0
@@ -126,6 +129,23 @@ class RadStats(C.Structure):
         ("rand_ms", C.c_double),
         ("rays_ms", C.c_double),
         ("bounce_ms", C.c_double),
+        ("total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ViewStats(C.Structure):
+    """struct fmgi_view_stats (include/flatmatch_gi.h)."""
+
+    _fields_ = [
+        ("cameras", C.c_int64),
+        ("rays", C.c_int64),
+        ("candidates", C.c_int64),
+        ("tests", C.c_int64),
+        ("cand_ms", C.c_double),
+        ("rays_ms", C.c_double),
         ("total_ms", C.c_double),
     ]
 
@@ -220,6 +240,9 @@ def load() -> C.CDLL:
         "fmgi_radiosity_jobs": (i64, [vp]),
         "fmgi_radiosity_stats": (C.c_int, [C.POINTER(RadStats)]),
         "fmgi_rand_skip": (C.c_int, [C.c_uint64]),
+        "fmgi_render_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+        "fmgi_view_candidates": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "fmgi_view_stats": (C.c_int, [C.POINTER(ViewStats)]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),
         "fmgi_filter_copy": (C.c_int, [vp, vp, vp, vp]),

@@ -135,6 +135,42 @@ int fmgi_radiosity_stats(fmgi_rad_stats *out);
    radiosity backend uses (as n rand() calls would). Returns 0 or FMGI_ERR_ARG (not glibc TYPE_3). */
 int fmgi_rand_skip(uint64_t n);
 
+/* ---- View renderer ------------------------------------------------------------ */
+/* The reference's debug raycaster (debugRaytracer.cc:121-176) on the GPU, for any pin-hole camera and for
+   batches of cameras. dir has any non-zero length, up is used as given, pixel is the size of one pixel on
+   the screen plane at distance 1 (the reference's dx = dy = (float)(1/1000.0)). */
+typedef struct fmgi_camera {
+    float pos[3], dir[3], up[3];
+    float pixel;
+} fmgi_camera;
+/* One image of width x height per camera: one ray per pixel from pos through
+   screenCenter + camRight * pixel * (x - width/2) - up * pixel * (y - height/2), traced with the reference's
+   getSortedIntersectableRects / findClosestIntersectionSorted (radiosityNative.c:25-90) over geo->walls.
+   All pointers are host pointers; outputs are [num_cams][height][width] (rgb_out: a trailing [3]) and any of
+   them may be NULL. wall_out = the index in geo->walls, texel_out = lightmapSetup[0] + getTileIdAt at the hit
+   point, dist_out = the hit distance; a miss gives -1, -1, +INFINITY. rgb_out = the three bytes of the hit
+   tile in tiles_rgb (fmgi_output_tiles' rgb_out, fmgi_output_tile_bytes(geo) bytes), or background.
+   Bit-identical to the reference's functions. Returns 0 or FMGI_ERR_*; argument errors (width or height < 1,
+   pixel not finite and positive, dir of zero length, more walls than the candidate sort holds, rgb_out
+   without tiles_rgb, a wall's texels outside [0, numTexels)) are reported before any device call. */
+int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                      const uint8_t *tiles_rgb, const uint8_t background[3], int32_t *wall_out,
+                      int32_t *texel_out, float *dist_out, uint8_t *rgb_out);
+/* One camera's sorted candidate list, computed on the device: returns its length and copies at most cap
+   entries (wall indices, minDistance values); a negative FMGI_ERR_* on failure. */
+int fmgi_view_candidates(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist,
+                         int cap);
+/* statistics of the last fmgi_render_views call (a struct tag: the function below carries the same name) */
+struct fmgi_view_stats {
+    int64_t cameras, rays;
+    int64_t candidates; /* list lengths summed over the cameras */
+    int64_t tests;      /* intersects() evaluations over all rays */
+    double cand_ms;     /* candidate lists */
+    double rays_ms;     /* ray casts */
+    double total_ms;    /* first upload .. last kernel */
+};
+int fmgi_view_stats(struct fmgi_view_stats *out);
+
 /* ---- Build-defined device-resident API ---------------------------------------------------------- */
 enum {
     FMGI_OK = 0,

@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""Record the REFERENCE's debug raycaster as fixtures (run where the reference checkout is present,
+FMGI_REFERENCE as for oracle/build_ref.sh, and that script has left the reference objects in oracle/_ref/obj).
+
+tests/golden/view_ref_main.c is linked, in a temporary directory, against the reference's own
+radiosityNative.o / rectangle.o / vector3_cl.o (+ the objects and libpng they pull in). For every case it
+runs the reference's getSortedIntersectableRects, findClosestIntersectionSorted and getTileIdAt over one
+camera's pixels (the loop of debugRaytracer.cc:121-176). tests/golden/view_ref.npz keeps, per case, the
+camera, the candidate list (wall index, minDistance bits), the per-pixel wall / texel / distance bits and
+the number of intersects() evaluations. tests/test_view.py checks a numpy restatement and the GPU against
+it. The counts below were measured with the reference objects and are asserted here.
+
+  python tests/golden/make_view_fixtures.py
+"""
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd")]
+from fmgi import scene  # noqa: E402
+
+REF = os.environ.get("FMGI_REFERENCE", "/root/reference")
+OBJ = os.path.join(REPO, "oracle", "_ref", "obj")
+PNG_INC = os.environ.get("PNG_INC", "/opt/conda/include")
+PNG_SO = os.environ.get("PNG_SO", "/usr/lib/x86_64-linux-gnu/libpng16.so.16")  # as oracle/build_ref.sh names it
+
+# camera: (pos, dir, up, pixel, W, H)
+CAM_A = ((5, 4, 1.3), (1, 0.5, -0.1), (0, 0, 1), 0.02, 64, 48)
+CAM_B = ((-5, 4, 1.3), (-1, 0, 0), (0, 0, 1), 0.02, 16, 8)
+CAM_C = ((5, 4, 20), (0, 0, -1), (0, 1, 0), 0.01, 67, 45)
+CAM_D = ((2.5, 2, 1.0), (1, 0, 0), (0, 0, 1), 0.05, 33, 17)
+
+# name: (scene, camera, candidates, hits, tests)
+CASES = {
+    "example_tool": ("example", ((5, 5.2, 1.6), (1, 1, 0), (0, 0, 1), 0.01, 67, 45), 122, 2551, 257776),
+    "example_plan": ("example", ((10, 7, 20), (0, 0, -1), (0, 1, 0), 0.01, 67, 45), 99, 1234, 281500),
+    "example_tool_pixel": ("example", ((5, 5.2, 1.6), (1, 1, 0), (0, 0, 1), 0.001, 64, 48), 122, 3072, 321941),
+    "box200_A": ("box200", CAM_A, 113, 3072, 219302),
+    "box200_C": ("box200", CAM_C, 164, 2565, 426620),
+    "box200_D": ("box200", CAM_D, 148, 561, 43720),
+    "box200_B": ("box200", CAM_B, 0, 0, 0),
+    "box2000_A": ("box2000", CAM_A, 1040, 3072, 1758001),
+    "box2000_C": ("box2000", CAM_C, 1600, 2565, 3779623),
+    "box2000_D": ("box2000", CAM_D, 1400, 561, 371172),
+    "box8_A": ("box8", CAM_A, 5, 3072, 12417),
+    "box8_C": ("box8", CAM_C, 5, 2565, 14645),
+}
+
+
+def get_scene(name):
+    if name == "example":
+        return scene.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example")
+    return {"box200": lambda: scene.box_scene(200, tile_size=2.0), "box2000": lambda: scene.box_scene(2000, tile_size=2.0),
+            "box8": lambda: scene.box_scene(8, tile_size=1.0)}[name]()
+
+
+def camera_words(cam):
+    """pos, dir, up, pixel as ten float32 values"""
+    pos, d, up, pixel = cam[:4]
+    return np.array([*pos, *d, *up, pixel], np.float32)
+
+
+def build(tmp):
+    exe = os.path.join(tmp, "view_ref")
+    cflags = ["-O2", "-msse3", "-std=c99", "-DNDEBUG", "-DCL_TARGET_OPENCL_VERSION=120", f"-I{REF}",
+              "-I/opt/rocm/include", f"-I{PNG_INC}", "-w"]
+    objs = [os.path.join(OBJ, f"{n}.o") for n in ("radiosityNative", "rectangle", "vector3_cl", "png_helper", "image",
+                                                   "helpers", "geometry")]
+    subprocess.run(["gcc", *cflags, "-o", exe, os.path.join(HERE, "view_ref_main.c"), *objs, PNG_SO, "-lm"], check=True)
+    return exe
+
+
+def run(exe, tmp, sc, cam):
+    g, o = os.path.join(tmp, "g.bin"), os.path.join(tmp, "o.bin")
+    scene.save_geometry(sc, g)
+    words = [f"{int(b):08x}" for b in camera_words(cam).view(np.uint32)]
+    subprocess.run([exe, g, o, str(cam[4]), str(cam[5]), *words], check=True)
+    raw = np.fromfile(o, np.int32)
+    nc, W, H = (int(x) for x in raw[:3])
+    pix = W * H
+    p = 3
+    cand = raw[p:p + 2 * nc].reshape(nc, 2)
+    p += 2 * nc
+    wall, texel, dist = (raw[p + k * pix:p + (k + 1) * pix].reshape(H, W) for k in range(3))
+    p += 3 * pix
+    tests = int(raw[p:p + 2].view(np.int64)[0])
+    assert p + 2 == len(raw)
+    return {"cand_wall": cand[:, 0].copy(), "cand_bits": cand[:, 1].copy().view(np.uint32), "wall": wall.copy(),
+            "texel": texel.copy(), "dist_bits": dist.copy().view(np.uint32), "tests": np.int64(tests)}
+
+
+def main():
+    out, meta, scenes = {}, {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = build(tmp)
+        for name, (sname, cam, ncand, hits, tests) in CASES.items():
+            sc = scenes.setdefault(sname, get_scene(sname))
+            r = run(exe, tmp, sc, cam)
+            got = (len(r["cand_wall"]), int((r["wall"] >= 0).sum()), int(r["tests"]))
+            print(name, *got, flush=True)
+            assert got == (ncand, hits, tests), (name, got, (ncand, hits, tests))
+            assert r["wall"].shape == (cam[5], cam[4])
+            for k, v in r.items():
+                out[f"{name}.{k}"] = v
+            out[f"{name}.camera"] = camera_words(cam)
+            meta[name] = {"scene": sname, "width": cam[4], "height": cam[5]}
+    out["meta"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(HERE, "view_ref.npz"), **out)
+
+
+if __name__ == "__main__":
+    main()
