@@ -59,8 +59,31 @@ struct ViewArgs {
     unsigned long long *tests; /* one counter: intersects() evaluations */
 };
 
+/*
+ * k_view_shade (fmgi_shade_views): samples x samples rays per pixel through the same walk, each coloured
+ * from the hit wall's tiles (nearest tile, or four taps clamped to the wall's own grid), resolved in fixed
+ * point. A lane keeps its pixel and loops the samples, so the candidate index stays wave-uniform; the integer
+ * sums make the result independent of the sample order. One launch covers the pixel window [x0, x1) x [y0, y1)
+ * of every camera; the host sizes the windows so that a launch casts at most FMGI_VIEW_MAX_RAYS rays.
+ */
+#define FMGI_VIEW_SAMPLES 8                       /* FMGI_VIEW_MAX_SAMPLES of the C ABI */
+#define FMGI_VIEW_MAX_RAYS ((int64_t)1 << 28)     /* rays per k_view_shade launch */
+
+struct ShadeArgs {
+    ViewArgs v;            /* as k_view_rays reads it; wall_out, texel_out, dist_out and tiles_rgb unused */
+    const uint32_t *tiles; /* one word per tile, r | g << 8 | b << 16, in wall order (null: no rgb) */
+    uint8_t *cov_out;      /* [ncams][height][width]: the pixel's rays that hit a wall, or null */
+    float offs[FMGI_VIEW_SAMPLES]; /* sample offsets in pixels, (2i + 1 - S) / 2S */
+    int samples;           /* S: 1 .. FMGI_VIEW_SAMPLES */
+    int filter;            /* 0 nearest, 1 bilinear */
+    int x0, y0, x1, y1;    /* this launch's pixels */
+};
+
 hipError_t fmgi_view_launch_candidates(const ViewArgs &a, hipStream_t s);
 hipError_t fmgi_view_launch_rays(const ViewArgs &a, hipStream_t s);
+/* RGB8 tiles -> one word per tile */
+hipError_t fmgi_view_launch_pack(const uint8_t *tiles_rgb, uint32_t *tiles, int64_t ntiles, hipStream_t s);
+hipError_t fmgi_view_launch_shade(const ShadeArgs &a, hipStream_t s);
 
 /* the radiosity backend's host images of a rectangle (fmgi_rad_host.cpp) */
 struct fmgi_rect;

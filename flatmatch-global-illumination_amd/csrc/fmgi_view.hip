@@ -72,11 +72,49 @@ __global__ __launch_bounds__(256) void k_view_candidates(ViewArgs a) {
     if (tid == 0) a.counts[c] = ncand;
 }
 
+/* debugRaytracer.cc:154-155: the ray through the screen point (fx, fy); add3 sums left to right */
+__device__ __forceinline__ v3 view_dir(const ViewCam &V, v3 cam, float fx, float fy) {
+    const v3 screen = add(add(mk(V.cx, V.cy, V.cz), mul(mk(V.rx, V.ry, V.rz), fx)), mul(mk(V.ux, V.uy, V.uz), fy));
+    return unit(sub(screen, cam));
+}
+
+/*
+ * findClosestIntersectionSorted (radiosityNative.c:67-90), the ray starting at camPos itself: the hit wall or
+ * -1, its distance in dist. The candidate index is uniform over the wave's lanes that are still walking (they
+ * all started at 0 together), so keys and rectangles are read once per wave.
+ */
+__device__ __forceinline__ int view_walk(const ViewArgs &a, const unsigned long long *keys, int C, v3 cam, v3 dir,
+                                         float &dist, unsigned long long &tests) {
+    dist = INFINITY;
+    int target = -1;
+    for (int i = 0; i < C; i++) {
+        const unsigned long long key = keys[i];
+        const float md = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32)));
+        if (dist < md) break;
+        const int idx = __builtin_amdgcn_readfirstlane((int)(uint32_t)key);
+        tests++;
+        const float dn = rect_intersects(a.hits[idx], cam, dir, dist);
+        if (dn < 0) continue;
+        if (dn <= dist) {
+            target = idx;
+            dist = dn;
+        }
+    }
+    return target;
+}
+
+/* getTileIdAt's tile coordinates before the cast (rectangle.c:205-230) */
+__device__ __forceinline__ void view_uv(const AoRect &t, const RadRect &tr, v3 cam, v3 dir, float dist, float &u,
+                                        float &v) {
+    const v3 pd = sub(add(cam, mul(dir, dist)), mk(t.px, t.py, t.pz));
+    const float dx = dot(mk(t.wx, t.wy, t.wz), pd), dy = dot(mk(t.hx, t.hy, t.hz), pd);
+    u = dx * (float)tr.s1 / t.wl;
+    v = dy * (float)tr.s2 / t.hl;
+}
+
 /*
  * One lane per pixel; a wave is an 8x8 pixel block, a workgroup 2x2 of them; blockIdx.z is the camera.
- * The candidate index is uniform over the wave's lanes that are still walking (they all started at 0), so
- * keys and rectangles are read once per wave. A lane outside the image does nothing but join the wave's
- * sum of its test counter with a zero.
+ * A lane outside the image does nothing but join the wave's sum of its test counter with a zero.
  */
 __global__ __launch_bounds__(256) void k_view_rays(ViewArgs a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -87,38 +125,18 @@ __global__ __launch_bounds__(256) void k_view_rays(ViewArgs a) {
     if (x < a.width && y < a.height) {
         const ViewCam V = a.cams[c];
         const v3 cam = mk(V.px, V.py, V.pz);
-        /* debugRaytracer.cc:154-155: add3 sums left to right */
         const float fx = V.pixel * (float)(x - a.width / 2), fy = -V.pixel * (float)(y - a.height / 2);
-        const v3 screen = add(add(mk(V.cx, V.cy, V.cz), mul(mk(V.rx, V.ry, V.rz), fx)), mul(mk(V.ux, V.uy, V.uz), fy));
-        const v3 dir = unit(sub(screen, cam));
-        /* findClosestIntersectionSorted (radiosityNative.c:67-90), the ray starting at camPos itself */
-        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n;
-        const int C = a.counts[c];
-        float dist = INFINITY;
-        int target = -1;
-        for (int i = 0; i < C; i++) {
-            const unsigned long long key = keys[i];
-            const float md = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32)));
-            if (dist < md) break;
-            const int idx = __builtin_amdgcn_readfirstlane((int)(uint32_t)key);
-            tests++;
-            const float dn = rect_intersects(a.hits[idx], cam, dir, dist);
-            if (dn < 0) continue;
-            if (dn <= dist) {
-                target = idx;
-                dist = dn;
-            }
-        }
+        const v3 dir = view_dir(V, cam, fx, fy);
+        float dist;
+        const int target = view_walk(a, a.keys + (size_t)c * a.sort_n, a.counts[c], cam, dir, dist, tests);
         int sid = -1;
         uint32_t rgb = a.background;
         if (target >= 0) {
-            /* getTileIdAt (rectangle.c:205-230) */
-            const AoRect t = a.hits[target];
             const RadRect tr = a.rects[target];
-            const v3 pd = sub(add(cam, mul(dir, dist)), mk(t.px, t.py, t.pz));
-            const float dx = dot(mk(t.wx, t.wy, t.wz), pd), dy = dot(mk(t.hx, t.hy, t.hz), pd);
-            const int tx = clampi(cvt_x86(dx * (float)tr.s1 / t.wl), 0, tr.s1 - 1);
-            const int ty = clampi(cvt_x86(dy * (float)tr.s2 / t.hl), 0, tr.s2 - 1);
+            float u, v;
+            view_uv(a.hits[target], tr, cam, dir, dist, u, v);
+            const int tx = clampi(cvt_x86(u), 0, tr.s1 - 1);
+            const int ty = clampi(cvt_x86(v), 0, tr.s2 - 1);
             const int tile = ty * tr.s1 + tx;
             sid = tr.s0 + tile;
             if (a.rgb_out) {
@@ -140,6 +158,95 @@ __global__ __launch_bounds__(256) void k_view_rays(ViewArgs a) {
     /* intersects() evaluations: counted per lane, one atomic per wave */
     const unsigned long long s = wave_sum(tests);
     if (lane == 0 && s) atomicAdd(a.tests, s);
+}
+
+__global__ __launch_bounds__(256) void k_view_pack(const uint8_t *rgb, uint32_t *out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (uint32_t)rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) | ((uint32_t)rgb[3 * i + 2] << 16);
+}
+
+/* one axis of the bilinear footprint: the two tile columns (clamped to the wall's grid) and the weight of the second */
+__device__ __forceinline__ void tap_axis(float u, int n, int &a, int &b, float &f) {
+    const float t = u - 0.5f, t0 = floorf(t);
+    f = t - t0;
+    a = clampi((int)t0, 0, n - 1);
+    b = clampi((int)t0 + 1, 0, n - 1);
+}
+
+__device__ __forceinline__ float lerp2(float f, float a, float b) { return (1.0f - f) * a + f * b; }
+
+/* the sample's fixed-point colour: (int)(val * 256 + 0.5) */
+__device__ __forceinline__ int fix8(float val) { return (int)(val * 256.0f + 0.5f); }
+
+/*
+ * k_view_rays's pixel mapping over the window [x0, x1) x [y0, y1). A lane loops its pixel's samples x samples
+ * rays: every lane of the wave starts each ray's walk at candidate 0 together, so view_walk's wave-uniform
+ * reads hold. Colours are summed as 24.8 fixed point, so the result does not depend on the sample order.
+ */
+__global__ __launch_bounds__(256) void k_view_shade(ShadeArgs s) {
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    unsigned long long tests = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool colour = a.rgb_out != nullptr, bilinear = s.filter != 0;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        const int bg0 = fix8((float)(a.background & 255)), bg1 = fix8((float)((a.background >> 8) & 255)),
+                  bg2 = fix8((float)((a.background >> 16) & 255));
+        int sum0 = 0, sum1 = 0, sum2 = 0, cov = 0;
+        for (int j = 0; j < S; j++) {
+            const float fy = -V.pixel * (py + s.offs[j]);
+            for (int i = 0; i < S; i++) {
+                const float fx = V.pixel * (px + s.offs[i]);
+                const v3 dir = view_dir(V, cam, fx, fy);
+                float dist;
+                const int target = view_walk(a, keys, C, cam, dir, dist, tests);
+                if (target < 0) {
+                    sum0 += bg0, sum1 += bg1, sum2 += bg2;
+                    continue;
+                }
+                cov++;
+                if (!colour) continue;
+                const RadRect tr = a.rects[target];
+                float u, v;
+                view_uv(a.hits[target], tr, cam, dir, dist, u, v);
+                const uint32_t *T = s.tiles + a.first_tile[target];
+                if (!bilinear) {
+                    const uint32_t w = T[clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1)];
+                    sum0 += fix8((float)(w & 255)), sum1 += fix8((float)((w >> 8) & 255)), sum2 += fix8((float)((w >> 16) & 255));
+                    continue;
+                }
+                int xa, xb, ya, yb;
+                float fu, fv;
+                tap_axis(u, tr.s1, xa, xb, fu);
+                tap_axis(v, tr.s2, ya, yb, fv);
+                const uint32_t w00 = T[ya * tr.s1 + xa], w01 = T[ya * tr.s1 + xb], w10 = T[yb * tr.s1 + xa],
+                               w11 = T[yb * tr.s1 + xb];
+#define FMGI_CH(sh)                                                                                        \
+    fix8(lerp2(fv, lerp2(fu, (float)((w00 >> sh) & 255), (float)((w01 >> sh) & 255)),                    \
+               lerp2(fu, (float)((w10 >> sh) & 255), (float)((w11 >> sh) & 255))))
+                sum0 += FMGI_CH(0), sum1 += FMGI_CH(8), sum2 += FMGI_CH(16);
+#undef FMGI_CH
+            }
+        }
+        const int64_t o = ((int64_t)c * a.height + y) * a.width + x;
+        if (colour) {
+            const int half = 128 * S * S, den = 256 * S * S;
+            uint8_t *q = a.rgb_out + 3 * o;
+            q[0] = (uint8_t)((sum0 + half) / den);
+            q[1] = (uint8_t)((sum1 + half) / den);
+            q[2] = (uint8_t)((sum2 + half) / den);
+        }
+        if (s.cov_out) s.cov_out[o] = (uint8_t)cov;
+    }
+    const unsigned long long n = wave_sum(tests);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
 }
 
 bool bad_sort(const ViewArgs &a) {
@@ -166,5 +273,26 @@ hipError_t fmgi_view_launch_rays(const ViewArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.width + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
                     (unsigned)((a.height + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
     hipLaunchKernelGGL(k_view_rays, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_pack(const uint8_t *tiles_rgb, uint32_t *tiles, int64_t ntiles, hipStream_t s) {
+    if (ntiles <= 0) return hipSuccess;
+    if (!tiles_rgb || !tiles || ntiles > (int64_t)0x7FFFFFFF * 256) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_view_pack, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, tiles_rgb, tiles, ntiles);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_shade(const ShadeArgs &s, hipStream_t st) {
+    const ViewArgs &a = s.v;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a) || a.ncams > FMGI_VIEW_MAX_BATCH || a.width < 1 || a.height < 1 ||
+        a.width > FMGI_VIEW_MAX_DIM || a.height > FMGI_VIEW_MAX_DIM || (a.rgb_out && (!s.tiles || !a.first_tile)) ||
+        s.samples < 1 || s.samples > FMGI_VIEW_SAMPLES || (s.filter != 0 && s.filter != 1) || s.x0 < 0 || s.y0 < 0 ||
+        s.x1 <= s.x0 || s.y1 <= s.y0 || s.x1 > a.width || s.y1 > a.height)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    hipLaunchKernelGGL(k_view_shade, grid, dim3(256), 0, st, s);
     return hipGetLastError();
 }

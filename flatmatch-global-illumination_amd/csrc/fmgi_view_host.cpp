@@ -7,7 +7,8 @@
  * The host checks every argument before the first device call, sets each camera up in fp32 in the
  * reference's order (built with -ffp-contract=off, no FMA), uploads the walls as the radiosity backend's
  * RadRect / AoRect images, runs the two kernels (fmgi_view.hip) over chunks of cameras and copies the
- * requested outputs back.
+ * requested outputs back. fmgi_shade_views (supersampled, filtered views; no reference program) takes the same
+ * path into k_view_shade, in launches of a bounded number of rays.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -58,12 +59,19 @@ struct Walls {
     int sort_n = 2;
 };
 
-int check_geometry(const fmgi_geometry *geo, Walls &w) {
-    if (!geo) return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: null geometry");
+/* an argument error of the entry point fn */
+int arg_err(const char *fn, const char *msg) {
+    char b[256];
+    snprintf(b, sizeof b, "%s: %s", fn, msg);
+    return internal_set_err(FMGI_ERR_ARG, b);
+}
+
+int check_geometry(const fmgi_geometry *geo, Walls &w, const char *fn) {
+    if (!geo) return arg_err(fn, "null geometry");
     if (geo->numWalls < 0 || geo->numTexels < 0 || (geo->numWalls && !geo->walls))
-        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: bad geometry");
+        return arg_err(fn, "bad geometry");
     if (geo->numWalls > FMGI_RAD_MAX_SORT)
-        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: more walls than the candidate sort holds (16384)");
+        return arg_err(fn, "more walls than the candidate sort holds (16384)");
     const int nr = geo->numWalls;
     w.rects.resize((size_t)std::max(nr, 1));
     w.hits.resize((size_t)std::max(nr, 1));
@@ -74,7 +82,7 @@ int check_geometry(const fmgi_geometry *geo, Walls &w) {
         const int32_t *lm = r.lightmapSetup;
         if (lm[1] < 1 || lm[2] < 1 || lm[0] < 0 || (int64_t)lm[1] * lm[2] > (1 << 28) ||
             (int64_t)lm[0] + (int64_t)lm[1] * lm[2] > geo->numTexels)
-            return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a wall's texels lie outside numTexels");
+            return arg_err(fn, "a wall's texels lie outside numTexels");
         w.rects[(size_t)i] = fmgi_rad_rect(r);
         w.hits[(size_t)i] = fmgi_rad_hit_rect(r);
         w.first_tile[(size_t)i] = tiles;
@@ -85,13 +93,13 @@ int check_geometry(const fmgi_geometry *geo, Walls &w) {
 }
 
 /* debugRaytracer.cc:121-125 */
-int make_cam(const fmgi_camera &c, ViewCam &o) {
+int make_cam(const fmgi_camera &c, ViewCam &o, const char *fn) {
     if (!(c.pixel > 0) || !isfinite(c.pixel))
-        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a camera's pixel size is not finite and positive");
+        return arg_err(fn, "a camera's pixel size is not finite and positive");
     const F3 pos{c.pos[0], c.pos[1], c.pos[2]}, d{c.dir[0], c.dir[1], c.dir[2]}, up{c.up[0], c.up[1], c.up[2]};
     const float len = length(d);
     if (!(len > 0) || !isfinite(len))
-        return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: a camera's direction has no length");
+        return arg_err(fn, "a camera's direction has no length");
     const F3 dir = normalized(d);
     const F3 centre = add(pos, dir);
     const F3 right = cross(dir, up);
@@ -114,8 +122,9 @@ int no_device() {
 int view_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
              const uint8_t *tiles_rgb, const uint8_t *background, int32_t *wall_out, int32_t *texel_out,
              float *dist_out, uint8_t *rgb_out) {
+    static const char fn[] = "fmgi_render_views";
     Walls w;
-    int rc = check_geometry(geo, w);
+    int rc = check_geometry(geo, w, fn);
     if (rc != FMGI_OK) return rc;
     if (width < 1 || height < 1 || width > FMGI_VIEW_MAX_DIM || height > FMGI_VIEW_MAX_DIM)
         return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: bad image size");
@@ -123,7 +132,7 @@ int view_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, in
     if (rgb_out && !tiles_rgb) return internal_set_err(FMGI_ERR_ARG, "fmgi_render_views: rgb_out needs tiles_rgb");
     std::vector<ViewCam> vc((size_t)std::max(num_cams, 1));
     for (int i = 0; i < num_cams; i++)
-        if ((rc = make_cam(cams[i], vc[(size_t)i])) != FMGI_OK) return rc;
+        if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
     memset(&g_stats, 0, sizeof g_stats);
     if (num_cams == 0) return FMGI_OK;
     if ((rc = no_device()) != FMGI_OK) return rc;
@@ -238,11 +247,11 @@ done:
 
 int candidates_run(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist, int cap) {
     Walls w;
-    int rc = check_geometry(geo, w);
+    int rc = check_geometry(geo, w, "fmgi_view_candidates");
     if (rc != FMGI_OK) return rc;
     if (!cam) return internal_set_err(FMGI_ERR_ARG, "fmgi_view_candidates: null camera");
     ViewCam vc;
-    if ((rc = make_cam(*cam, vc)) != FMGI_OK) return rc;
+    if ((rc = make_cam(*cam, vc, "fmgi_view_candidates")) != FMGI_OK) return rc;
     if ((rc = no_device()) != FMGI_OK) return rc;
     RadRect *d_rects = nullptr;
     ViewCam *d_cams = nullptr;
@@ -286,7 +295,155 @@ done:
     return rc;
 }
 
+static_assert(FMGI_VIEW_SAMPLES == FMGI_VIEW_MAX_SAMPLES, "kernel and ABI sample limits differ");
+
+/* a device allocation that lives as long as its scope */
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
+    template <class T> T *as() const { return (T *)p; }
+};
+
+/* rays per k_view_shade launch: FMGI_VIEW_MAX_RAYS, or FMGI_VIEW_RAYS_PER_LAUNCH from the environment (tests
+   use it to reach the windowed launches with small images) */
+int64_t shade_ray_budget() {
+    const char *e = getenv("FMGI_VIEW_RAYS_PER_LAUNCH");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? std::min<int64_t>(v, FMGI_VIEW_MAX_RAYS) : FMGI_VIEW_MAX_RAYS;
+}
+
+int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+              const uint8_t *tiles_rgb, const uint8_t *background, int samples, int filter, uint8_t *rgb_out,
+              uint8_t *coverage_out) {
+    static const char fn[] = "fmgi_shade_views";
+    Walls w;
+    int rc = check_geometry(geo, w, fn);
+    if (rc != FMGI_OK) return rc;
+    if (width < 1 || height < 1 || width > FMGI_VIEW_MAX_DIM || height > FMGI_VIEW_MAX_DIM)
+        return arg_err(fn, "bad image size");
+    if (num_cams < 0 || (num_cams && !cams)) return arg_err(fn, "bad cameras");
+    if (rgb_out && !tiles_rgb) return arg_err(fn, "rgb_out needs tiles_rgb");
+    if (samples < 1 || samples > FMGI_VIEW_MAX_SAMPLES) return arg_err(fn, "samples outside 1..8");
+    if (filter != FMGI_VIEW_NEAREST && filter != FMGI_VIEW_BILINEAR) return arg_err(fn, "filter is neither nearest nor bilinear");
+    std::vector<ViewCam> vc((size_t)std::max(num_cams, 1));
+    for (int i = 0; i < num_cams; i++)
+        if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
+    memset(&g_stats, 0, sizeof g_stats);
+    if (num_cams == 0) return FMGI_OK;
+    if ((rc = no_device()) != FMGI_OK) return rc;
+
+    const int nr = geo->numWalls;
+    const int64_t pix = (int64_t)width * height, spp = (int64_t)samples * samples, budget = shade_ray_budget();
+    /* cameras per launch: at most 2^26 pixels of outputs on the device, and at most `budget` rays */
+    const int batch = (int)std::max<int64_t>(
+        1, std::min<int64_t>({(int64_t)num_cams, FMGI_VIEW_MAX_BATCH, ((int64_t)1 << 26) / pix, budget / (pix * spp)}));
+    /* one camera over the budget: windows of whole workgroup rows, then of workgroup columns */
+    int rows = height, cols = width;
+    if (pix * spp > budget) {
+        const int64_t B = FMGI_VIEW_BLOCK;
+        rows = (int)std::min<int64_t>(height, std::max<int64_t>(B, budget / ((int64_t)width * spp) / B * B));
+        cols = (int)std::min<int64_t>(width, std::max<int64_t>(B, budget / ((int64_t)rows * spp) / B * B));
+    }
+    const int64_t ntiles = nr ? w.first_tile[(size_t)nr - 1] + (int64_t)geo->walls[nr - 1].lightmapSetup[1] * geo->walls[nr - 1].lightmapSetup[2] : 0;
+    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_tests, d_rgb, d_cov, d_first, d_tiles;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<int32_t> counts((size_t)batch);
+    unsigned long long tests = 0;
+    ShadeArgs s;
+    memset(&s, 0, sizeof s);
+    ViewArgs &a = s.v;
+    {
+        const char *dv = getenv("FMGI_DEVICE");
+        VIEWCHK(hipSetDevice(dv ? atoi(dv) : 0));
+    }
+    for (auto &e : ev) VIEWCHK(hipEventCreate(&e));
+    VIEWCHK(hipEventRecord(ev[0], nullptr));
+    VIEWCHK(d_rects.alloc(w.rects.size() * sizeof(RadRect)));
+    VIEWCHK(hipMemcpy(d_rects.p, w.rects.data(), w.rects.size() * sizeof(RadRect), hipMemcpyHostToDevice));
+    VIEWCHK(d_hits.alloc(w.hits.size() * sizeof(AoRect)));
+    VIEWCHK(hipMemcpy(d_hits.p, w.hits.data(), w.hits.size() * sizeof(AoRect), hipMemcpyHostToDevice));
+    VIEWCHK(d_cams.alloc((size_t)batch * sizeof(ViewCam)));
+    VIEWCHK(d_keys.alloc((size_t)batch * w.sort_n * 8));
+    VIEWCHK(d_counts.alloc((size_t)batch * 4));
+    VIEWCHK(d_tests.alloc(8));
+    VIEWCHK(hipMemset(d_tests.p, 0, 8));
+    if (coverage_out) VIEWCHK(d_cov.alloc((size_t)batch * pix));
+    if (rgb_out) {
+        VIEWCHK(d_rgb.alloc((size_t)batch * pix * 3));
+        VIEWCHK(d_first.alloc(w.first_tile.size() * 8));
+        VIEWCHK(hipMemcpy(d_first.p, w.first_tile.data(), w.first_tile.size() * 8, hipMemcpyHostToDevice));
+        /* the RGB8 tiles go up as they are and are repacked to one word per tile on the device */
+        DevBuf d_bytes;
+        VIEWCHK(d_bytes.alloc((size_t)ntiles * 3));
+        VIEWCHK(d_tiles.alloc((size_t)ntiles * 4));
+        if (ntiles) VIEWCHK(hipMemcpy(d_bytes.p, tiles_rgb, (size_t)ntiles * 3, hipMemcpyHostToDevice));
+        VIEWCHK(fmgi_view_launch_pack(d_bytes.as<uint8_t>(), d_tiles.as<uint32_t>(), ntiles, nullptr));
+        VIEWCHK(hipStreamSynchronize(nullptr));
+    }
+    a.rects = d_rects.as<RadRect>();
+    a.hits = d_hits.as<AoRect>();
+    a.nrects = nr;
+    a.sort_n = w.sort_n;
+    a.cams = d_cams.as<ViewCam>();
+    a.width = width;
+    a.height = height;
+    a.keys = d_keys.as<unsigned long long>();
+    a.counts = d_counts.as<int32_t>();
+    a.first_tile = d_first.as<int64_t>();
+    a.background = background ? ((uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16)) : 0;
+    a.rgb_out = d_rgb.as<uint8_t>();
+    a.tests = d_tests.as<unsigned long long>();
+    s.tiles = d_tiles.as<uint32_t>();
+    s.cov_out = d_cov.as<uint8_t>();
+    s.samples = samples;
+    s.filter = filter;
+    for (int i = 0; i < samples; i++) s.offs[i] = (float)(2 * i + 1 - samples) / (float)(2 * samples);
+    for (int c0 = 0; c0 < num_cams; c0 += batch) {
+        const int n = std::min(batch, num_cams - c0);
+        const size_t px = (size_t)n * pix, o = (size_t)c0 * pix;
+        a.ncams = n;
+        VIEWCHK(hipMemcpy(d_cams.p, vc.data() + c0, (size_t)n * sizeof(ViewCam), hipMemcpyHostToDevice));
+        VIEWCHK(hipEventRecord(ev[1], nullptr));
+        VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+        VIEWCHK(hipEventRecord(ev[2], nullptr));
+        for (s.y0 = 0; s.y0 < height; s.y0 += rows)
+            for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
+                s.y1 = std::min(height, s.y0 + rows);
+                s.x1 = std::min(width, s.x0 + cols);
+                VIEWCHK(fmgi_view_launch_shade(s, nullptr));
+            }
+        VIEWCHK(hipEventRecord(ev[3], nullptr));
+        VIEWCHK(hipEventSynchronize(ev[3]));
+        float ms = 0;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+        g_stats.cand_ms += ms;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        g_stats.rays_ms += ms;
+        VIEWCHK(hipEventElapsedTime(&ms, ev[0], ev[3]));
+        g_stats.total_ms = ms;
+        VIEWCHK(hipMemcpy(counts.data(), d_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) g_stats.candidates += counts[(size_t)i];
+        if (rgb_out) VIEWCHK(hipMemcpy(rgb_out + 3 * o, d_rgb.p, px * 3, hipMemcpyDeviceToHost));
+        if (coverage_out) VIEWCHK(hipMemcpy(coverage_out + o, d_cov.p, px, hipMemcpyDeviceToHost));
+    }
+    VIEWCHK(hipMemcpy(&tests, d_tests.p, 8, hipMemcpyDeviceToHost));
+    g_stats.cameras = num_cams;
+    g_stats.rays = (int64_t)num_cams * pix * spp;
+    g_stats.tests = (int64_t)tests;
+done:
+    for (auto &e : ev)
+        if (e) hipEventDestroy(e);
+    return rc;
+}
+
 } // namespace
+
+FMGI_API int fmgi_shade_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                              const uint8_t *tiles_rgb, const uint8_t background[3], int samples, int filter,
+                              uint8_t *rgb_out, uint8_t *coverage_out) {
+    return shade_run(geo, cams, num_cams, width, height, tiles_rgb, background, samples, filter, rgb_out, coverage_out);
+}
 
 FMGI_API int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
                                const uint8_t *tiles_rgb, const uint8_t background[3], int32_t *wall_out,

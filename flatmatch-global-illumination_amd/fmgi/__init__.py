@@ -21,7 +21,7 @@ from . import scene
 
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
-                   ViewStats, check, load)
+                   VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
 LAUNCH_DTYPE = np.dtype(
@@ -57,6 +57,7 @@ __all__ = [
     "CAMERA_DTYPE",
     "camera",
     "render_views",
+    "shade_views",
     "view_candidates",
     "view_stats",
 ]
@@ -477,6 +478,38 @@ def render_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray
     return out
 
 
+_VIEW_FILTERS = {"nearest": VIEW_NEAREST, "bilinear": VIEW_BILINEAR}
+
+
+def shade_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray | None = None, background=(0, 0, 0),
+                samples: int = 1, filter: str = "nearest") -> dict:
+    """Supersampled, filtered camera views (fmgi_shade_views): samples x samples rays per pixel, each coloured
+    from the hit wall's tiles ("nearest": the tile it lands in, "bilinear": the four around it, clamped to the
+    wall) or `background`, averaged in fixed point. Returns {"coverage"} (uint8 [cameras, height, width]: the
+    pixel's rays that hit a wall) and, when tiles_rgb is given, {"rgb"} (uint8, a trailing [3]). samples=1 with
+    "nearest" gives render_views' rgb."""
+    lib = load()
+    if filter not in _VIEW_FILTERS:
+        raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
+    cams = _cameras(cams)
+    n = len(cams)
+    g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+    tiles = None if tiles_rgb is None else np.ascontiguousarray(tiles_rgb, np.uint8)
+    if tiles is not None and len(tiles) != lib.fmgi_output_tile_bytes(C.byref(g)):
+        raise FmgiError(f"tiles_rgb holds {len(tiles)} bytes, the scene's tiles take {lib.fmgi_output_tile_bytes(C.byref(g))}")
+    out = {"coverage": np.empty((n, height, width), np.uint8)}
+    if tiles is not None:
+        out["rgb"] = np.empty((n, height, width, 3), np.uint8)
+    bg = np.array(background, np.uint8)
+    assert bg.shape == (3,)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(lib.fmgi_shade_views(C.byref(g), p(cams), n, width, height, None if tiles is None else p(tiles), p(bg),
+                               samples, _VIEW_FILTERS[filter], p(out["rgb"]) if tiles is not None else None,
+                               p(out["coverage"])), "fmgi_shade_views")
+    del keep
+    return out
+
+
 def view_candidates(sc: Scene, cam):
     """One camera's sorted candidate list from the device (fmgi_view_candidates): (wall indices int32,
     minDistance float32), in the order the rays walk it."""
@@ -494,7 +527,7 @@ def view_candidates(sc: Scene, cam):
 
 
 def view_stats() -> dict:
-    """fmgi_view_stats: the last render_views call's cameras, rays, candidates, intersects() tests and times."""
+    """fmgi_view_stats: the last render_views or shade_views call's cameras, rays, candidates, intersects() tests and times."""
     st = ViewStats()
     check(load().fmgi_view_stats(C.byref(st)), "fmgi_view_stats")
     return st.as_dict()

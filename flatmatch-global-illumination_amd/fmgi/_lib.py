@@ -68,6 +68,7 @@ EXPORTS = (
     "fmgi_render_views",
     "fmgi_view_candidates",
     "fmgi_view_stats",
+    "fmgi_shade_views",
 )
 
 KERNEL_EXACT = 0
@@ -80,6 +81,9 @@ ACCUM_FX3 = 1
 ACCUM_STATE = 2
 ACCUM_NONE = 3  # profiling only: deposits discarded
 ACCUM_STREAM = 4
+VIEW_NEAREST = 0
+VIEW_BILINEAR = 1
+VIEW_MAX_SAMPLES = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
            "no_axes": 7}
@@ -243,6 +247,7 @@ def load() -> C.CDLL:
         "fmgi_render_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
         "fmgi_view_candidates": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "fmgi_view_stats": (C.c_int, [C.POINTER(ViewStats)]),
+        "fmgi_shade_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),
         "fmgi_filter_copy": (C.c_int, [vp, vp, vp, vp]),

@@ -160,7 +160,24 @@ int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num
    entries (wall indices, minDistance values); a negative FMGI_ERR_* on failure. */
 int fmgi_view_candidates(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist,
                          int cap);
-/* statistics of the last fmgi_render_views call (a struct tag: the function below carries the same name) */
+/* Supersampled, filtered views for looking at a bake: samples x samples rays per pixel, sample (i, j) offset by
+   ((2i + 1 - samples) / (2 samples), (2j + 1 - samples) / (2 samples)) pixels from fmgi_render_views' ray, each
+   traced by the same walk. A sample that misses has the background's colour; one that hits wall t at tile
+   coordinates (u, v) (getTileIdAt's, before the cast) has the tile's bytes (NEAREST), or the bilinear blend of
+   the four tiles around (u - 0.5, v - 0.5), taps clamped to t's own s1 x s2 grid (BILINEAR), all fp32. Each
+   sample's colour goes to fixed point, q = (int)(colour * 256 + 0.5), and the pixel's byte is
+   (sum q + 128 samples^2) / (256 samples^2) in integers, so the result is exact and independent of order.
+   rgb_out [num_cams][height][width][3]; coverage_out [num_cams][height][width] = how many of the pixel's rays
+   hit a wall (0..samples^2); either may be NULL; rgb_out needs tiles_rgb. Host pointers. samples = 1 with
+   NEAREST gives fmgi_render_views' rgb_out. Argument errors: those of fmgi_render_views, samples outside
+   1..FMGI_VIEW_MAX_SAMPLES, filter not one of the two; all reported before any device call. */
+enum { FMGI_VIEW_NEAREST = 0, FMGI_VIEW_BILINEAR = 1 };
+#define FMGI_VIEW_MAX_SAMPLES 8
+int fmgi_shade_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                     const uint8_t *tiles_rgb, const uint8_t background[3], int samples, int filter,
+                     uint8_t *rgb_out, uint8_t *coverage_out);
+/* statistics of the last fmgi_render_views or fmgi_shade_views call (rays = cameras * width * height *
+   samples^2 after the latter; a struct tag: the function below carries the same name) */
 struct fmgi_view_stats {
     int64_t cameras, rays;
     int64_t candidates; /* list lengths summed over the cameras */

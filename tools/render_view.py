@@ -11,6 +11,9 @@ reference's debug raycaster paints.
   python tools/render_view.py box200 --texels out/texels.npy --spa 172413793 --pos 5 4 1.3 --dir 1 0.5 -0.1 \\
       --pixel 0.002 --width 1024 --height 768 -o view.ppm
 
+With --samples N (N x N rays per pixel, up to 8) and / or --filter bilinear the picture comes from
+fmgi.shade_views instead: supersampled edges and linearly filtered tiles, as a viewer of the tiles draws them.
+
 A PNG is written next to the PPM when PIL can be imported.
 """
 import argparse
@@ -62,6 +65,8 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=3072)
     ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
+    ap.add_argument("--samples", type=int, default=1, help="N x N rays per pixel (1..8)")
+    ap.add_argument("--filter", choices=("nearest", "bilinear"), default="nearest", help="how a ray reads the tiles")
     ap.add_argument("-o", "--output", default="view.ppm")
     a = ap.parse_args(argv)
     import fmgi
@@ -75,10 +80,15 @@ def main(argv=None):
     else:
         tiles = wall_colour_tiles(sc)
     cam = fmgi.camera(a.pos, a.dir, a.up, a.pixel)
-    out = fmgi.render_views(sc, cam, a.width, a.height, tiles_rgb=tiles, background=tuple(a.background))
+    if a.samples == 1 and a.filter == "nearest":
+        out = fmgi.render_views(sc, cam, a.width, a.height, tiles_rgb=tiles, background=tuple(a.background))
+        hits, unit = int((out["wall"] >= 0).sum()), "pixels"
+    else:
+        out = fmgi.shade_views(sc, cam, a.width, a.height, tiles, tuple(a.background), samples=a.samples, filter=a.filter)
+        hits, unit = int(out["coverage"].sum(dtype=np.int64)), "rays"
     write_ppm(a.output, out["rgb"][0])
     st = fmgi.view_stats()
-    print(f"{a.output}: {a.width}x{a.height}, {int((out['wall'] >= 0).sum())} of {st['rays']} pixels hit a wall, "
+    print(f"{a.output}: {a.width}x{a.height}, {hits} of {st['rays']} {unit} hit a wall, "
           f"{st['candidates']} candidates, {st['tests'] / max(st['rays'], 1):.1f} tests/ray, {st['total_ms']:.2f} ms")
     try:
         from PIL import Image
