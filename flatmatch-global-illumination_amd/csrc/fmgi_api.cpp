@@ -940,13 +940,16 @@ static uint64_t dense_cap_for(uint64_t items, int grid, int block) {
 /* pool blocks for `cap` codes: the codes, the sentinel pads (<= 3 per tile and ring flush: a flush per
    FMGI_RING_CODES codes plus each wave's last), one partly filled block per wave and tile, and the
    blocks a wave holds reserved (< FMGI_BUCKET_ALLOC) */
-static uint64_t bucket_pool_blocks(uint64_t cap, int P, int grid, int block) {
+/* (the shared layout, kAccShared: no pads; per workgroup and tile the two blocks published ahead and one being
+   opened, and the rest of the tile's reserve) */
+static uint64_t bucket_pool_blocks(uint64_t cap, int P, int grid, int block, bool shared) {
+    if (shared) return (cap + FMGI_BUCKET_BLOCK - 1) / FMGI_BUCKET_BLOCK + (uint64_t)grid * (uint64_t)P * (3u + FMGI_SHARED_ALLOC) + 8;
     const uint64_t waves = (uint64_t)grid * (uint64_t)(block / 64);
     const uint64_t pads = (cap / FMGI_RING_CODES + waves) * 3u * (uint64_t)P;
     return (cap + pads + FMGI_BUCKET_BLOCK - 1) / FMGI_BUCKET_BLOCK + waves * (uint64_t)(P + FMGI_BUCKET_ALLOC) + 8;
 }
-static uint64_t stream_alloc_codes(uint64_t cap, int P, int grid, int block, int mode) {
-    return mode >= kStreamBuckets ? bucket_pool_blocks(cap, P, grid, block) * FMGI_BUCKET_BLOCK : cap;
+static uint64_t stream_alloc_codes(uint64_t cap, int P, int grid, int block, int mode, bool shared) {
+    return mode >= kStreamBuckets ? bucket_pool_blocks(cap, P, grid, block, shared) * FMGI_BUCKET_BLOCK : cap;
 }
 
 /* fold tiles of 2^bits texels over the lightmap */
@@ -957,30 +960,37 @@ static int tiles_of(const fmgi_context *c, int bits) { return (c->num_texels + (
    ~22 instead of ~34 lines (box200 bake 65.7 -> 60.8 ms), while the fold's 96-KB accumulators run one
    workgroup per CU (fold +1.2 ms whatever the chunk: example.png's 1e8 photons lose overall, 22.6 -> 23.2 ms;
    profiles/r05/s16). So: wide from 3e6 work items (3e8 photons) per chunk. FMGI_WIDE_TILES=0/1 forces. */
-static int tile_bits(const fmgi_context *c, int mode, uint64_t items) {
+static const uint64_t kWideTileItems = 3000000;
+/* (shared_box: the closed box filled through per-workgroup blocks, kAccShared. A CU then has 2 x 46 open lines
+   instead of 24 x 46, the wide tiles' fewer lines per store buy nothing (bake 58.3 against 58.4 ms on box200)
+   and the narrow tiles' fold is 1.9 ms faster: narrow whatever the chunk; profiles/shared_buckets) */
+static int tile_bits(const fmgi_context *c, int mode, uint64_t items, bool shared_box) {
     if (mode < kStreamBuckets) return FMGI_TILE_BITS;
     if (c->opt[FMGI_OPT_WIDE_TILES] >= 0) return c->opt[FMGI_OPT_WIDE_TILES] ? FMGI_WIDE_TILE_BITS : FMGI_TILE_BITS;
     if (const char *we = fmgi_exp_env("FMGI_WIDE_TILES")) { /* experiments: 0 / 1 (= 12) or the tile bits, 11-13 */
         const int v = atoi(we);
         return v == 1 ? FMGI_WIDE_TILE_BITS : (v >= 11 && v <= 13 ? v : FMGI_TILE_BITS);
     }
-    return items >= 3000000 ? FMGI_WIDE_TILE_BITS : FMGI_TILE_BITS;
+    if (shared_box) return FMGI_TILE_BITS;
+    return items >= kWideTileItems ? FMGI_WIDE_TILE_BITS : FMGI_TILE_BITS;
 }
 
-static bool ensure_stream_needs_growth(const fmgi_context *c, int k, uint64_t items, int grid, int block, int mode) {
+static bool ensure_stream_needs_growth(const fmgi_context *c, int k, uint64_t items, int grid, int block, int mode,
+                                       bool shared) {
     const int P = tiles_of(c, FMGI_TILE_BITS);
-    return stream_alloc_codes(stream_cap_for(items, grid, block), P, grid, block, mode) > c->sb_cap_alloc[k] ||
+    return stream_alloc_codes(stream_cap_for(items, grid, block), P, grid, block, mode, shared) > c->sb_cap_alloc[k] ||
            (mode == kStreamSliced && !c->sb[k].sorted) ||
            (mode == kStreamDense && dense_cap_for(items, grid, block) > c->sb[k].dense_alloc);
 }
 
-static int ensure_stream(fmgi_context *c, int k, uint64_t items, int grid, int block, int mode, int tbits) {
+static int ensure_stream(fmgi_context *c, int k, uint64_t items, int grid, int block, int mode, int tbits,
+                         bool shared) {
     StreamBufs &sb = c->sb[k];
     const uint64_t cap = stream_cap_for(items, grid, block);
     /* (the pool is sized for the narrow tiles' open blocks: enough for either) */
     const int P = tiles_of(c, FMGI_TILE_BITS);
     sb.tile_bits = tbits;
-    const uint64_t codes = stream_alloc_codes(cap, P, grid, block, mode);
+    const uint64_t codes = stream_alloc_codes(cap, P, grid, block, mode, shared);
     if (codes > c->sb_cap_alloc[k] || (mode == kStreamSliced && !sb.sorted)) {
         hipFree(sb.stream);
         hipFree(sb.sorted);
@@ -1008,7 +1018,7 @@ static int ensure_stream(fmgi_context *c, int k, uint64_t items, int grid, int b
        bucketed stream's per-block tile, length and list instead */
     uint64_t entries = 0;
     if (mode >= kStreamBuckets) {
-        sb.pool_blocks = bucket_pool_blocks(cap, P, grid, block);
+        sb.pool_blocks = bucket_pool_blocks(cap, P, grid, block, shared);
         /* FMGI_OPT_POOL_LIMIT = n (tests): at most n pool blocks, so the bake runs out of them and takes the
            exact atomic fallback (bucket_atomic) for the rest of its codes */
         if (c->opt[FMGI_OPT_POOL_LIMIT] > 0)
@@ -1621,13 +1631,16 @@ static int kernel_instance(const fmgi_context *c, int kernel) {
     return kernel == FMGI_KERNEL_GRID && grid_axes_scene(c) ? (kernel | FMGI_KVAR_AXES) : kernel;
 }
 
+/* the accumulations that store lane by lane (no rings: built for 6 waves per SIMD, every table staged) */
+static bool acc_by_lane(int accum) { return accum == kAccScatter || accum == kAccShared; }
+
 static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool trace) {
     StagePlan p;
     const char *be = fmgi_exp_env("FMGI_BLOCK");
     const int forced_block = (be && atoi(be) >= 64 && atoi(be) <= 1024 && atoi(be) % 64 == 0) ? atoi(be) : 0;
     p.block = forced_block ? forced_block : 256;
     if (kernel == FMGI_KERNEL_EXACT) return p; /* no LDS image: nothing is staged */
-    if (c->compact && kernel == FMGI_KERNEL_GRID && accum == kAccScatter && c->nsrcs > 0 && !forced_block) {
+    if (c->compact && kernel == FMGI_KERNEL_GRID && acc_by_lane(accum) && c->nsrcs > 0 && !forced_block) {
         /* the compact closed box: image | emitters | classes | RectC | filter extents | cells, one 1024-lane
            workgroup per CU (the tables take most of its LDS) */
         int off = (c->gimg_bytes + 15) & ~15;
@@ -1666,7 +1679,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
        CU, keep the grid cells staged beside the walls at 24 waves per CU, which 512-lane ones (three per CU)
        cannot */
     const int blocks_ring[] = {256, 512, 1024}, blocks_scatter[] = {256, 512, 768, 1024};
-    const bool scat = accum == kAccScatter;
+    const bool scat = acc_by_lane(accum);
     const int *blocks_all = scat ? blocks_scatter : blocks_ring;
     const int nblocks = scat ? 4 : 3;
     /* the grid cells in LDS: every cell lookup an LDS read instead of an L2 one. The closed boxes' coarse
@@ -1678,7 +1691,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
     const bool cells_forced = ce && atoi(ce) == 1 && kernel == FMGI_KERNEL_GRID;
     bool cells = cells_forced || (!ce && c->cells_lds && kernel == FMGI_KERNEL_GRID);
     auto best = [&](bool rects, int &bb, int &bw) {
-        const int bytes = stage_bytes(c, kernel, rects, srcs, cells, accum == kAccScatter, nullptr, nullptr);
+        const int bytes = stage_bytes(c, kernel, rects, srcs, cells, scat, nullptr, nullptr);
         bb = p.block;
         bw = waves(p.block, bytes);
         if (forced_block) return;
@@ -1712,7 +1725,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
         }
     }
     p.block = rects ? b1 : b0;
-    p.bytes = stage_bytes(c, kernel, rects, srcs, cells, accum == kAccScatter, &p.rects_off, &p.srcs_off, &p.cells_off,
+    p.bytes = stage_bytes(c, kernel, rects, srcs, cells, scat, &p.rects_off, &p.srcs_off, &p.cells_off,
                           &p.grecs_off,
                           &p.gidx_off);
     return p;
@@ -1808,7 +1821,8 @@ static int exec_accum(const fmgi_context *c) {
        completions never hold up a load's s_waitcnt (box200: bake 76.7 -> 69.3 ms at 6 instead of 4 waves per
        SIMD; box2000, whose 2000 walls stay in L2: 132 ms with the rings, 160 with scattered stores; profiles/
        r05/s5). FMGI_SCATTER=0/1 forces either (experiments, tests). */
-    if (c->opt[FMGI_OPT_BUCKET_FILL] >= 0) return c->opt[FMGI_OPT_BUCKET_FILL] ? kAccScatter : kAccBucket; /* tests */
+    if (c->opt[FMGI_OPT_BUCKET_FILL] >= 0) /* tests, A/B runs: 0 the rings, 1 per-wave blocks, 2 per-workgroup blocks */
+        return c->opt[FMGI_OPT_BUCKET_FILL] == 2 ? kAccShared : (c->opt[FMGI_OPT_BUCKET_FILL] ? kAccScatter : kAccBucket);
     if (c->compact) return kAccScatter; /* the compact closed box: every table staged (FMGI_KVAR_COMPACT) */
     const size_t tables = (size_t)c->nrects * sizeof(RectLds) + (c->cells_lds ? (size_t)c->grid_cells * sizeof(GridCell) : 0);
     return tables <= 64 * 1024 ? kAccScatter : kAccBucket;
@@ -1844,11 +1858,26 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
        the tables' size, the plan whether they were staged): a plan that left the walls, or a closed box's
        cells, in global memory takes the rings instead (box2000 before its compact tables: 160 ms scattered,
        132 ms with the rings) */
-    if (kacc == kAccScatter && c->opt[FMGI_OPT_BUCKET_FILL] < 0 && !c->compact &&
+    if (acc_by_lane(kacc) && c->opt[FMGI_OPT_BUCKET_FILL] < 0 && !c->compact &&
         ((c->nrects > 0 && sp.rects_off < 0) || (c->cells_lds && kernel == FMGI_KERNEL_GRID && sp.cells_off < 0)) &&
         fitting_kernel(c, kernel, kAccBucket, bake_block()) == kernel) {
         kacc = kAccBucket;
         sp = plan_stage(c, kernel, kacc, trace);
+    }
+    /* AUTO, per-workgroup tile blocks (kAccShared) where they measured faster than the per-wave ones in the same
+       process (profiles/shared_buckets): the closed box with every table staged (box200: bake +
+       fold 70.7 -> 66.1 ms, on 2048-texel tiles, tile_bits below) and the hybrid scan's launches on narrow
+       tiles (example.png: 21.5 -> 20.7 ms). The compact closed box gained nothing (box2000: 82.6 ms either
+       way) and keeps the per-wave blocks; the other scans and the hybrid scan on wide tiles were not measured. */
+    if (kacc == kAccScatter && c->opt[FMGI_OPT_BUCKET_FILL] < 0 && !c->compact) {
+        const StagePlan q = plan_stage(c, kernel, kAccShared, trace);
+        const bool staged = q.rects_off >= 0 && q.srcs_off >= 0 && q.cells_off >= 0 && q.grecs_off >= 0 &&
+                            c->ngeneral == 0;
+        if ((kernel == FMGI_KERNEL_GRID && grid_axes_scene(c) && staged) ||
+            (kernel == FMGI_KERNEL_HYBRID && e - b < kWideTileItems && !(c->nrects > 0 && q.rects_off < 0))) {
+            kacc = kAccShared;
+            sp = q;
+        }
     }
     const int block = sp.block;
     /* the closed box with every table staged (walls, emitters, grid cells) launches the instance whose
@@ -2199,7 +2228,7 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
     int tail_coop = 0;
     if (const char *te = fmgi_exp_env("FMGI_TAIL")) tail_coop = atoi(te);
     const bool tail = kernel == FMGI_KERNEL_HYBRID && inst == FMGI_KERNEL_HYBRID && !trace && a.coop == 1 &&
-                      (kacc == kAccScatter || kacc == kAccBucket) && (tail_coop == 1 || tail_coop == 2 || tail_coop == 4) &&
+                      (acc_by_lane(kacc) || kacc == kAccBucket) && (tail_coop == 1 || tail_coop == 2 || tail_coop == 4) &&
                       e - b <= 16 * (uint64_t)lanes;
     const int inst1 = tail ? FMGI_KERNEL_HYBRID_TAIL : inst;
     for (uint64_t cb = b; cb < e; cb += chunk, nchunk++) {
@@ -2215,12 +2244,12 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
            happens only while growing, after a full wait) */
         if (overlap && nchunk >= 2) HIPCHK(hipStreamWaitEvent(s, c->ev_folded[k], 0));
         /* (the pool holds one partly filled block per wave and tile: the resuming launch's waves too) */
-        if (ensure_stream_needs_growth(c, k, ce - cb, grid + grid2, block, smode)) { /* no fold may still read it */
+        if (ensure_stream_needs_growth(c, k, ce - cb, grid + grid2, block, smode, kacc == kAccShared)) { /* no fold may still read it */
             HIPCHK(hipStreamSynchronize(s));
             if (c->fold_stream) HIPCHK(hipStreamSynchronize(c->fold_stream));
         }
-        const int tbits = tile_bits(c, smode, ce - cb);
-        int rc = ensure_stream(c, k, ce - cb, grid + grid2, block, smode, tbits);
+        const int tbits = tile_bits(c, smode, ce - cb, kacc == kAccShared && kernel == FMGI_KERNEL_GRID);
+        int rc = ensure_stream(c, k, ce - cb, grid + grid2, block, smode, tbits, kacc == kAccShared);
         if (rc != FMGI_OK) return rc;
         StreamBufs &sb = c->sb[k];
         a.item_begin = cb;
@@ -2460,6 +2489,7 @@ FMGI_API int fmgi_get_stats(fmgi_context *c, fmgi_stats *out) {
     out->rescans_tie = v[KSTAT_TIES];
     out->rescans_invalid = v[KSTAT_INVALID];
     out->stream_overflow = v[KSTAT_OVERFLOW];
+    out->bucket_fallback_codes = v[KSTAT_FALLBACK];
     return FMGI_OK;
 }
 

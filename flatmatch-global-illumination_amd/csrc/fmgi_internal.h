@@ -208,7 +208,8 @@ struct BakeArgs {
 };
 
 enum { KSTAT_PHOTONS = 0, KSTAT_SCANS, KSTAT_DEPOSITS, KSTAT_ESCAPES, KSTAT_RESCANS, KSTAT_TESTS, KSTAT_TIES,
-       KSTAT_INVALID, KSTAT_N, KSTAT_OVERFLOW = KSTAT_N, KSTAT_STAGE0 = 16, KSTAT_ALLOC = 32 };
+       KSTAT_INVALID, KSTAT_N, KSTAT_OVERFLOW = KSTAT_N, KSTAT_FALLBACK /* AccShared: codes added by bucket_atomic */,
+       KSTAT_STAGE0 = 16, KSTAT_ALLOC = 32 };
 
 /* stream accumulation geometry (fmgi_accum.hip) */
 #define FMGI_STREAM_BLOCK 4096 /* codes reserved per wave at a time                         */
@@ -295,6 +296,11 @@ constexpr int kAccScatter = 7; /* the bucket layout stored lane by lane into per
 #endif
 constexpr int kAccDense = 8; /* a dense code stream (one code or sentinel per lane and iteration), binned by k_bin */
 constexpr int kAccSliced = 9; /* the STREAM's unsorted layout alone (BakeArgs::presort 0, AccStreamT<0>) */
+constexpr int kAccShared = 10; /* the bucket layout stored lane by lane into per-workgroup tile blocks (AccShared) */
+/* AccShared: LDS dwords per workgroup (64 tile words, 64 x 4 published blocks, init's broadcast word, 64 reserves; u64 each) */
+#define FMGI_SHARED_RING 4
+#define FMGI_SHARED_ALLOC 8 /* pool blocks a tile's opener reserves at a time, at most */
+#define FMGI_SHARED_DWORDS (2 * (64 + 64 * FMGI_SHARED_RING + 2 + 64))
 /* `kernel` of the bake launch helpers below: the public FMGI_KERNEL_* id, or FMGI_KERNEL_GRID |
    FMGI_KVAR_AXES for the closed-box instance of the grid scan (BakeArgs::grid_axes set) */
 #define FMGI_KVAR_AXES 0x100

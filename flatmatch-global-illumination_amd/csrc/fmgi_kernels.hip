@@ -1913,6 +1913,175 @@ struct AccScatter {
     }
 };
 
+/*
+ * The lane-by-lane stores with the open blocks shared by a workgroup's waves (kAccShared). AccScatter keeps one
+ * open block per wave and tile: 24 waves x 23 tiles = 552 partly written lines per CU on box200. Here the
+ * workgroup keeps, per fold tile t, one word W[t] = {fill (low 32), seq (high 32)} and a ring R[t][4] of
+ * published blocks {tag = seq (low 32), block id (high 32)}; block `seq` of the tile is R[t][seq & 3] while its
+ * tag says so. Nothing is staged and no lane ever waits for another:
+ *   - a depositing lane adds 1 to W[t] (one returning 64-bit LDS add) and gets (rank, seq): rank < BP is slot
+ *     rank of block seq, BP <= rank < 2 BP slot rank - BP of block seq + 1 (published one block earlier, so
+ *     nobody depends on an opener's pool atomic), rank >= 2 BP the exact int64 fallback (bucket_atomic);
+ *   - the lane with rank == BP is the one opener of (t, seq): it records block seq full, takes block seq + 2
+ *     from the tile's reserve, publishes it, and then moves the word on with one add of {-BP, +1}. The ring
+ *     entry a lane reads was therefore stored before the word value that sent it there. The reserve is one
+ *     LDS word V[t] = {next, end} of pool blocks per tile, which only the tile's opener touches (a tile has
+ *     one opener at a time), refilled with one pool-cursor atomic for up to kBatch blocks (fewer while the
+ *     tile has filled few blocks, so a tile that gets little leaves little unused). One reserve per
+ *     workgroup, refilled by whichever opener found it empty, lost a batch whenever two tiles' openers
+ *     refilled at once, which was the rule, and ran the pool dry (profiles/shared_buckets/README.md).
+ *   - Ranks past 2 BP hold no slot: they are the first F - 2 BP positions of block seq + 2 in the new numbering
+ *     (F: the fill the opener's add returned). No lane will ever get rank == BP of seq + 1 then, so the same
+ *     lane goes on as that seq's opener: it stores sentinels (which the fold skips) in those slots and repeats
+ *     the step. After kChain such steps it closes the tile for this workgroup instead (fill bit kClosed: the
+ *     lengths of its two blocks are final, every later code takes the fallback), so the loop is bounded.
+ * Exactness: every position below 2 BP of a seq is one slot of one block, written once by its lane or as a
+ * sentinel by the opener, and a block's recorded length covers exactly the positions handed out; every other
+ * code is added by bucket_atomic. A ring entry is overwritten two block switches (two pool atomics) after
+ * its block filled up; a lane that still finds another tag between its add and its read of the ring (two LDS
+ * operations back to back) adds its code exactly too, but its slot would be read unwritten, so it raises the
+ * overflow flag and the call fails (never seen; the tests assert 0). The blocks are the bucket layout
+ * k_bucket_fold reads. LDS: 3.1 KB per workgroup against 6 KB for the 12 per-wave tables.
+ */
+struct AccShared {
+    typedef unsigned long long u64;
+    typedef __attribute__((address_space(1))) uint32_t gu32;
+    static constexpr uint32_t BP = FMGI_BUCKET_BLOCK, kNoBlock = 0xFFFFFFFFu, kSent = 0xFFFFFFFFu;
+    static constexpr uint32_t NR = FMGI_SHARED_RING;
+    static constexpr uint32_t kClosed = 1u << 30; /* fill bit: the tile takes the fallback from here on */
+    static constexpr int kChain = 8;              /* opener steps of one lane before it closes the tile */
+    static constexpr uint32_t kBatch = FMGI_SHARED_ALLOC; /* pool blocks a refill of a reserve takes, at most */
+    static __device__ __forceinline__ int layout(const BakeArgs &) { return 2; }
+    static __device__ __forceinline__ void deposit(const BakeArgs &, int, int, f3) {}
+    static __device__ __forceinline__ u64 *word(uint32_t *base) { return (u64 *)base; }
+    static __device__ __forceinline__ u64 *ring(uint32_t *base) { return (u64 *)base + 64; }
+    static __device__ __forceinline__ u64 *reserve(uint32_t *base) { return (u64 *)base + 64 + 64 * NR + 2; }
+    static __device__ __forceinline__ u64 ld(const u64 *p) {
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+
+    /* blocks seq 0 and 1 of every tile: 2 P consecutive pool blocks, one atomic per workgroup (kNoBlock where
+       the pool cannot supply them) */
+    static __device__ __forceinline__ void init(const BakeArgs &a, uint32_t *base) {
+        u64 *W = word(base), *R = ring(base), *bc = ring(base) + 64 * NR;
+        const uint32_t P = (uint32_t)a.ntiles;
+        if (threadIdx.x == 0) *bc = atomicAdd(a.pool_cursor, (u64)(2u * P));
+        __syncthreads();
+        const u64 first = *bc;
+        for (uint32_t t = threadIdx.x; t < 64u; t += blockDim.x) {
+            W[t] = 0ull;
+            reserve(base)[t] = 0ull;
+#pragma unroll
+            for (uint32_t k = 0; k < NR; k++) {
+                const u64 id = first + 2u * t + k;
+                const uint32_t b = (t < P && k < 2u && id < a.pool_blocks) ? (uint32_t)id : kNoBlock;
+                if (b != kNoBlock) a.block_tile[b] = t;
+                R[t * NR + k] = ((u64)b << 32) | (k < 2u ? k : 0xFFFFFFFFu); /* (tag ~0: not published) */
+            }
+        }
+        __syncthreads();
+    }
+
+    /* a block of tile t's reserve V = {next, end} (kNoBlock once the pool is exhausted); by the tile's opener */
+    static __device__ __forceinline__ uint32_t take(const BakeArgs &a, u64 *V, uint32_t t, uint32_t seq) {
+        const u64 v = ld(V);
+        if ((uint32_t)v < (uint32_t)(v >> 32)) {
+            __hip_atomic_store(V, v + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return (uint32_t)v;
+        }
+        const uint32_t want = seq / 4u + 1u < kBatch ? seq / 4u + 1u : kBatch;
+        const u64 first = atomicAdd(a.pool_cursor, (u64)want);
+        if (first >= a.pool_blocks) return kNoBlock;
+        const u64 hi = first + want < a.pool_blocks ? first + want : a.pool_blocks;
+        /* the batch's other blocks: the tile's, empty until an opener records them full (its release fence
+           below completes these stores before the tile can have another opener) */
+#pragma nounroll
+        for (uint32_t b = (uint32_t)first + 1u; b < (uint32_t)hi; b++) a.block_tile[b] = t, a.block_len[b] = 0u;
+        __hip_atomic_store(V, (hi << 32) | (first + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return (uint32_t)first;
+    }
+
+    /* the opener of (t, seq), see above: one lane, rarely */
+    static __device__ __forceinline__ void open(const BakeArgs &a, u64 *W, u64 *R, u64 *V, uint32_t t, uint32_t seq) {
+        uint32_t holes = 0; /* leading slots of block seq + 1 whose positions took the fallback */
+        for (int step = 0;; step++, seq++) {
+            const uint32_t cb = (uint32_t)(ld(R + t * NR + (seq & (NR - 1))) >> 32);
+            const uint32_t nb1 = (uint32_t)(ld(R + t * NR + ((seq + 1) & (NR - 1))) >> 32);
+            if (cb != kNoBlock) a.block_len[cb] = BP;
+            if (nb1 != kNoBlock) {
+#pragma nounroll
+                for (uint32_t i = 0; i < (holes < BP ? holes : BP); i++) ((gu32 *)a.stream)[(uint64_t)nb1 * BP + i] = kSent;
+            }
+            if (step == kChain) { /* close the tile: block seq + 1 ends with the last position handed out */
+                const uint32_t F = (uint32_t)__hip_atomic_fetch_add(W + t, (u64)kClosed, __ATOMIC_RELAXED,
+                                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (nb1 != kNoBlock) a.block_len[nb1] = F - BP < BP ? F - BP : BP;
+                return;
+            }
+            const uint32_t nb = take(a, V + t, t, seq);
+            if (nb != kNoBlock) a.block_tile[nb] = t;
+            __hip_atomic_store(R + t * NR + ((seq + 2) & (NR - 1)), ((u64)nb << 32) | (seq + 2), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+            /* (LDS operations of a wave complete in order: the entry is in place before the word moves on) */
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            const uint32_t F = (uint32_t)__hip_atomic_fetch_add(W + t, (1ull << 32) - BP, __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (F <= 2 * BP) return;
+            holes = F - 2 * BP;
+        }
+    }
+
+    /* a code that holds no slot: added exactly, and counted (`lost`: its slot stays unwritten, see above) */
+    static __device__ __forceinline__ void fallback(const BakeArgs &a, uint32_t code, bool lost) {
+        if (lost) atomicAdd(a.overflow, 1ull);
+        atomicAdd(a.stats + KSTAT_FALLBACK, 1ull);
+        AccBucket::bucket_atomic(a, code);
+    }
+
+    static __device__ __forceinline__ void append(const BakeArgs &a, WaveStream &, uint32_t *base, bool dep,
+                                                  uint32_t code) {
+        if (!dep) return;
+        u64 *W = word(base), *R = ring(base);
+        const uint32_t t = code >> uni(a.tile_shift);
+        const u64 old = __hip_atomic_fetch_add(W + t, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t rank = (uint32_t)old, seq = (uint32_t)(old >> 32);
+        const uint32_t next = rank >= BP ? 1u : 0u, want = seq + next;
+        /* (the address depends on the add's result: read after it, and after the entry was published) */
+        const u64 e = ld(R + t * NR + (want & (NR - 1)));
+        const uint32_t tag = (uint32_t)e, blk = (uint32_t)(e >> 32);
+        /* (one condition, no short circuit: the store is the loop's straight path) */
+        const bool ok = (rank < 2 * BP) & (tag == want) & (blk != kNoBlock);
+        if (__builtin_expect(ok, 1)) {
+            ((gu32 *)a.stream)[(uint64_t)blk * BP + (rank - next * BP)] = code;
+        } else {
+            fallback(a, code, rank < 2 * BP && tag != want);
+        }
+        /* (the opener's own code, slot 0 of block seq + 1, is stored by now: its registers are free) */
+        if (rank == BP) open(a, W, R, reserve(base), t, seq);
+    }
+
+    /* after the loop, once every wave of the workgroup has stored its codes: one lane per tile records the
+       lengths of the tile's current and next block (a published block that got no code: length 0, tile 0; the
+       reserves' blocks were recorded empty when they were taken) */
+    static __device__ __forceinline__ void finish(const BakeArgs &a, WaveStream &, uint32_t *base) {
+        __syncthreads();
+        const u64 *W = word(base), *R = ring(base);
+        for (uint32_t t = threadIdx.x; t < (uint32_t)a.ntiles; t += blockDim.x) {
+            const u64 w = W[t];
+            const uint32_t fill = (uint32_t)w, seq = (uint32_t)(w >> 32);
+            if (fill >= kClosed) continue; /* closed by its opener, which recorded both lengths */
+            const uint32_t len[2] = {fill < BP ? fill : BP, fill > BP ? (fill - BP < BP ? fill - BP : BP) : 0u};
+#pragma unroll
+            for (uint32_t k = 0; k < 2; k++) {
+                const uint32_t b = (uint32_t)(R[t * NR + ((seq + k) & (NR - 1))] >> 32);
+                if (b == kNoBlock) continue;
+                a.block_len[b] = len[k];
+                if (len[k] == 0) a.block_tile[b] = 0u;
+            }
+        }
+    }
+};
+
 #if FMGI_EXPERIMENTS
 /*
  * The dense stream (kAccDense): the bake only writes, the fold's binning pass (k_bin, fmgi_accum.hip) sorts.
@@ -1994,6 +2163,10 @@ template <>
 struct HasAppend<AccScatter> {
     static constexpr bool value = true;
 };
+template <>
+struct HasAppend<AccShared> {
+    static constexpr bool value = true;
+};
 template <int Mode>
 struct HasAppend<AccStreamT<Mode>> {
     static constexpr bool value = true;
@@ -2023,6 +2196,10 @@ __device__ __forceinline__ uint32_t *acc_region<AccLines>(char *lds, const BakeA
 template <>
 __device__ __forceinline__ uint32_t *acc_region<AccScatter>(char *lds, const BakeArgs &a) {
     return (uint32_t *)(lds + a.ring_off) + (threadIdx.x >> 6) * FMGI_SCATTER_STRIDE;
+}
+template <>
+__device__ __forceinline__ uint32_t *acc_region<AccShared>(char *lds, const BakeArgs &a) {
+    return (uint32_t *)(lds + a.ring_off); /* one table per workgroup */
 }
 
 /* ---- the per-lane photon state machine ------------------------------------------------------- */
@@ -2184,6 +2361,8 @@ constexpr int acc_min_waves<AccLines>() { return 6; }
 #endif
 template <>
 constexpr int acc_min_waves<AccScatter>() { return FMGI_SCATTER_WAVES; }
+template <>
+constexpr int acc_min_waves<AccShared>() { return FMGI_SCATTER_WAVES; }
 #if FMGI_EXPERIMENTS
 template <>
 constexpr int acc_min_waves<AccDense>() { return FMGI_SCATTER_WAVES; }
@@ -2624,6 +2803,7 @@ const void *kernel_acc(int accum, bool trace) {
     if (accum == kAccSliced) return kernel_ptr<Scan, AccSliced>(trace);
     if (accum == kAccBucket) return kernel_ptr<Scan, AccBucket>(trace);
     if (accum == kAccScatter) return kernel_ptr<Scan, AccScatter>(trace);
+    if (accum == kAccShared) return kernel_ptr<Scan, AccShared>(trace);
 #if FMGI_EXPERIMENTS
     if (accum == 4) return kernel_ptr<Scan, AccStream>(trace);
     if (accum == kAccLines) return kernel_ptr<Scan, AccLines>(trace);
@@ -2641,6 +2821,7 @@ bool launch_acc(const BakeArgs &a, int accum, bool trace, dim3 grid, dim3 block,
     else if (accum == kAccSliced) launch3<Scan, AccSliced>(a, trace, grid, block, lds, s);
     else if (accum == kAccBucket) launch3<Scan, AccBucket>(a, trace, grid, block, lds, s);
     else if (accum == kAccScatter) launch3<Scan, AccScatter>(a, trace, grid, block, lds, s);
+    else if (accum == kAccShared) launch3<Scan, AccShared>(a, trace, grid, block, lds, s);
 #if FMGI_EXPERIMENTS
     else if (accum == 4) launch3<Scan, AccStream>(a, trace, grid, block, lds, s);
     else if (accum == kAccLines) launch3<Scan, AccLines>(a, trace, grid, block, lds, s);
@@ -2656,6 +2837,7 @@ const void *bake_kernel(int kernel, int accum, bool trace) {
     if (kernel == FMGI_KERNEL_FAST_COOP)
         return accum == kAccBucket ? kernel_ptr<ScanFastCoop, AccBucket>(false)
                : accum == kAccScatter ? kernel_ptr<ScanFastCoop, AccScatter>(false)
+               : accum == kAccShared ? kernel_ptr<ScanFastCoop, AccShared>(false)
                : accum == kAccSliced ? kernel_ptr<ScanFastCoop, AccSliced>(false)
 #if FMGI_EXPERIMENTS
                : accum == kAccLines ? kernel_ptr<ScanFastCoop, AccLines>(false)
@@ -2666,15 +2848,18 @@ const void *bake_kernel(int kernel, int accum, bool trace) {
 #if FMGI_EXPERIMENTS
     if (kernel == FMGI_KERNEL_HYBRID_TAIL) /* the launch-tail pair: lane-by-lane stores and the rings */
         return accum == kAccScatter ? kernel_ptr<ScanHybridTail, AccScatter>(false)
+               : accum == kAccShared ? kernel_ptr<ScanHybridTail, AccShared>(false)
                : accum == kAccBucket ? kernel_ptr<ScanHybridTail, AccBucket>(false) : nullptr;
     if (kernel == FMGI_KERNEL_HYBRID_RESUME)
         return accum == kAccScatter ? kernel_ptr<ScanHybridResume, AccScatter>(false)
+               : accum == kAccShared ? kernel_ptr<ScanHybridResume, AccShared>(false)
                : accum == kAccBucket ? kernel_ptr<ScanHybridResume, AccBucket>(false) : nullptr;
 #else
     if (kernel == FMGI_KERNEL_HYBRID_TAIL || kernel == FMGI_KERNEL_HYBRID_RESUME) return nullptr;
 #endif
     if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) /* the lane-by-lane stores only (bake_common) */
-        return accum == kAccScatter ? kernel_ptr<ScanGridAxesCompact, AccScatter>(trace) : nullptr;
+        return accum == kAccScatter ? kernel_ptr<ScanGridAxesCompact, AccScatter>(trace)
+               : accum == kAccShared ? kernel_ptr<ScanGridAxesCompact, AccShared>(trace) : nullptr;
     if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) return kernel_acc<ScanGridAxesStaged>(accum, trace);
     if (kernel == (2 | FMGI_KVAR_AXES)) return kernel_acc<ScanGridAxes>(accum, trace);
 #if FMGI_EXPERIMENTS
@@ -2701,6 +2886,7 @@ size_t fmgi_bake_lds(int kernel, int accum, int block, int img_bytes, int *ring_
     if (accum == kAccLines) return img + (size_t)FMGI_LINES_DWORDS * 4;
 #endif
     if (accum == kAccScatter) return img + (size_t)(block / 64) * FMGI_SCATTER_STRIDE * 4;
+    if (accum == kAccShared) return img + (size_t)FMGI_SHARED_DWORDS * 4;
     if (accum == kAccBucket) return img + (size_t)(block / 64) * FMGI_RING_STRIDE_BUCKET * 4;
     return img + ((accum == 4 || accum == kAccSliced) ? (size_t)(block / 64) * FMGI_RING_STRIDE * 4 : 0);
 }
@@ -2760,6 +2946,7 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
         if (trace || !bake_kernel(kernel, accum, false)) return hipErrorInvalidValue;
         if (accum == kAccBucket) launch3<ScanFastCoop, AccBucket>(a, false, grid, blk, lds, s);
         else if (accum == kAccScatter) launch3<ScanFastCoop, AccScatter>(a, false, grid, blk, lds, s);
+        else if (accum == kAccShared) launch3<ScanFastCoop, AccShared>(a, false, grid, blk, lds, s);
         else if (accum == kAccSliced) launch3<ScanFastCoop, AccSliced>(a, false, grid, blk, lds, s);
 #if FMGI_EXPERIMENTS
         else if (accum == kAccDense) launch3<ScanFastCoop, AccDense>(a, false, grid, blk, lds, s);
@@ -2772,6 +2959,8 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
     } else if (kernel == FMGI_KERNEL_HYBRID_TAIL || kernel == FMGI_KERNEL_HYBRID_RESUME) { /* the launch tail */
         if (trace || !bake_kernel(kernel, accum, false)) return hipErrorInvalidValue;
         if (kernel == FMGI_KERNEL_HYBRID_TAIL && accum == kAccScatter) launch3<ScanHybridTail, AccScatter>(a, false, grid, blk, lds, s);
+        else if (kernel == FMGI_KERNEL_HYBRID_TAIL && accum == kAccShared) launch3<ScanHybridTail, AccShared>(a, false, grid, blk, lds, s);
+        else if (accum == kAccShared) launch3<ScanHybridResume, AccShared>(a, false, grid, blk, lds, s);
         else if (kernel == FMGI_KERNEL_HYBRID_TAIL) launch3<ScanHybridTail, AccBucket>(a, false, grid, blk, lds, s);
         else if (accum == kAccScatter) launch3<ScanHybridResume, AccScatter>(a, false, grid, blk, lds, s);
         else launch3<ScanHybridResume, AccBucket>(a, false, grid, blk, lds, s);
@@ -2779,8 +2968,9 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
     } else if (kernel == 4) { /* FMGI_KERNEL_HYBRID */
         ok = launch_acc<ScanHybrid>(a, accum, trace, grid, blk, lds, s);
     } else if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) { /* closed box, the compact tables in LDS */
-        if (accum != kAccScatter) return hipErrorInvalidValue;
-        launch3<ScanGridAxesCompact, AccScatter>(a, trace, grid, blk, lds, s);
+        if (accum == kAccShared) launch3<ScanGridAxesCompact, AccShared>(a, trace, grid, blk, lds, s);
+        else if (accum != kAccScatter) return hipErrorInvalidValue;
+        else launch3<ScanGridAxesCompact, AccScatter>(a, trace, grid, blk, lds, s);
     } else if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) { /* closed box, every table in LDS */
         ok = launch_acc<ScanGridAxesStaged>(a, accum, trace, grid, blk, lds, s);
     } else if (kernel == (2 | FMGI_KVAR_AXES)) { /* FMGI_KERNEL_GRID, closed box */

@@ -104,6 +104,7 @@ class Stats(C.Structure):
         ("rescans_tie", C.c_uint64),
         ("rescans_invalid", C.c_uint64),
         ("stream_overflow", C.c_uint64),
+        ("bucket_fallback_codes", C.c_uint64),
     ]
 
     def as_dict(self):

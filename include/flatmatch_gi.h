@@ -230,6 +230,10 @@ typedef struct fmgi_stats {
     uint64_t rescans_tie;     /* exact_rescans caused by a runner-up within the separation band */
     uint64_t rescans_invalid; /* exact_rescans caused by a phase-1 winner that is not exactly valid */
     uint64_t stream_overflow; /* STREAM: reservations past the stream capacity (must stay 0) */
+    uint64_t bucket_fallback_codes; /* STREAM, per-workgroup tile blocks: codes added to the lightmap with
+                                       device atomics instead of being stored (exact; 0 unless a workgroup
+                                       hits one tile much harder than a block per pool atomic, or the pool
+                                       is exhausted) */
 } fmgi_stats;
 
 /* One work item of the flattened reference launch schedule (global_illumination_cl.c:246-267). */
@@ -347,7 +351,8 @@ int fmgi_experiments(void);
      FMGI_OPT_CHUNK_ITEMS   > 0: at most this many work items per STREAM chunk (several chunks per call)
      FMGI_OPT_POOL_LIMIT    > 0: at most this many bucket-pool blocks (the exact atomic fallback takes the rest)
      FMGI_OPT_STREAM_LAYOUT 0: the slice-sorted stream (lightmaps of more than 63 tiles); -1: by the scene
-     FMGI_OPT_BUCKET_FILL   0: per-wave LDS rings, 1: lane-by-lane stores; -1: by the tables' LDS fit
+     FMGI_OPT_BUCKET_FILL   0: per-wave LDS rings, 1: lane-by-lane stores into per-wave tile blocks, 2: into
+                            per-workgroup tile blocks; -1: by the tables' LDS fit
      FMGI_OPT_WIDE_TILES    0 / 1: 2048- / 4096-texel bucket tiles; -1: by the launch size
      FMGI_OPT_COOP          2, 4, 8: lanes per work item of ScanFast's small launches; 0: by the launch size
      FMGI_OPT_NO_AXES       1: closed boxes through the general grid instance (its sorted <= 4-slot phase 1) */
