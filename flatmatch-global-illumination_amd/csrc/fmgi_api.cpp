@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -31,6 +32,7 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_internal.h"
+#include "fmgi_recolour.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
 
@@ -710,6 +712,15 @@ struct fmgi_context {
     int accum = FMGI_ACCUM_FX3;
     unsigned long long *d_counts = nullptr;
     long long *d_colfx = nullptr;
+    /* fmgi_bake_states: the caller's histogram that bake_common's AccState launch counts into (no fold) */
+    unsigned long long *ext_counts = nullptr;
+    /* fmgi_recolour: the calls' tables on the device (u32 [launch][1024][k][3]) and their host side, both reused
+       by the next call once ev_recolour (recorded after a call's last launch) has completed */
+    uint32_t *d_recolour_tab = nullptr;
+    size_t recolour_tab_cap = 0;
+    std::vector<uint32_t> h_recolour_tab;
+    hipEvent_t ev_recolour = nullptr;
+    bool recolour_pending = false;
     uint32_t *d_colpack = nullptr; /* the same table as u32 {r, g, b, 0} (STREAM fold) */
     /* STREAM: deposit-code stream + fold buffers, grown on demand (fmgi_accum.hip); two sets, so the
        fold of one chunk (on fold_stream) overlaps the bake of the next */
@@ -841,6 +852,8 @@ FMGI_API void fmgi_destroy(fmgi_context *c) {
     hipFree(c->d_fetch_tab);
     hipFree(c->d_counts);
     hipFree(c->d_colfx);
+    if (c->ev_recolour) { hipEventSynchronize(c->ev_recolour); hipEventDestroy(c->ev_recolour); }
+    hipFree(c->d_recolour_tab);
     if (c->fold_stream) hipStreamSynchronize(c->fold_stream);
     for (int k = 0; k < 2; k++) {
         hipFree(c->sb[k].stream);
@@ -2047,7 +2060,7 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
     }
     a.general = c->d_general;
     a.ngeneral = c->ngeneral;
-    a.counts = c->accum == FMGI_ACCUM_STATE ? c->d_counts : nullptr;
+    a.counts = c->accum == FMGI_ACCUM_STATE ? (c->ext_counts ? c->ext_counts : c->d_counts) : nullptr;
     a.num_texels = c->num_texels;
     a.events = events;
     a.ev_counts = counts;
@@ -2184,8 +2197,9 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
                                             a.coop > 1 ? -1 : inst),
                                 block, s));
         HIPCHK(time_end(c, s, t0, t1, c->ev_bake));
-        /* AccState: fold the (state, texel) counters into the int64 lightmap and zero them */
-        if (a.counts)
+        /* AccState: fold the (state, texel) counters into the int64 lightmap and zero them (fmgi_bake_states
+           keeps them: the histogram is the result) */
+        if (a.counts && !c->ext_counts)
             HIPCHK(fmgi_launch_reduce_states(a.counts, c->d_colfx, (unsigned long long *)lm, c->num_texels, s));
         HIPCHK(finish_call());
         return FMGI_OK;
@@ -2402,6 +2416,161 @@ FMGI_API int fmgi_bake_items(fmgi_context *c, uint64_t item_begin, uint64_t item
     if (!c) return set_err(FMGI_ERR_ARG, "null context");
     return bake_common(c, item_begin, item_end, lm_fx_dev, kernel, stream ? (hipStream_t)stream : c->stream, false,
                        nullptr, nullptr, nullptr);
+}
+
+/* ---- per-state photon histograms and their recolouring ---- */
+
+FMGI_API void fmgi_palette_reference(fmgi_palette *p) {
+    if (!p) return;
+    const fmgi_palette ref = {{18, 18, 18}, {16, 16, 18}, {1.0f, 0.85f, 0.7f}, 0.9f}; /* photonmap.cl:167-169, 241-249 */
+    *p = ref;
+}
+
+/* colour_table() with the palette's constants in place of photonmap.cl's (x * 1.0f keeps x's bits, so the
+   reference palette gives colour_table()'s values) */
+static bool palette_ok(const fmgi_palette *p) {
+    for (int k = 0; k < 3; k++) {
+        const float w = p->window_rgb[k], l = p->light_rgb[k], t = p->floor_tint[k];
+        if (!std::isfinite(w) || !std::isfinite(l) || !std::isfinite(t)) return false;
+        if (!(w >= 0 && w < 32 && l >= 0 && l < 32 && t >= 0 && t <= 1)) return false;
+    }
+    return std::isfinite(p->albedo) && p->albedo >= 0 && p->albedo <= 1;
+}
+
+static void palette_fill(const fmgi_palette *p, int64_t *t) {
+    for (int sid = 0; sid < FMGI_COLOUR_STATES; sid++) {
+        int64_t *o = t + 3 * sid;
+        o[0] = o[1] = o[2] = 0;
+        const int s = sid & 511;
+        if (s == 0) continue;
+        const float *e = (sid & 512) ? p->window_rgb : p->light_rgb;
+        f3 c = mkf3(e[0], e[1], e[2]);
+        int nb = 0;
+        while ((s >> (nb + 1)) != 0) nb++; /* bits below the leading 1 = diffuse bounces */
+        for (int b = nb - 1; b >= 0; b--) {
+            if ((s >> b) & 1) {
+                c.x *= p->floor_tint[0];
+                c.y *= p->floor_tint[1];
+                c.z *= p->floor_tint[2];
+            }
+            c = mul3(c, p->albedo);
+        }
+        o[0] = (int64_t)ldexp((double)c.x, FMGI_FX_SHIFT);
+        o[1] = (int64_t)ldexp((double)c.y, FMGI_FX_SHIFT);
+        o[2] = (int64_t)ldexp((double)c.z, FMGI_FX_SHIFT);
+    }
+}
+
+FMGI_API int fmgi_palette_table(const fmgi_palette *p, int64_t table[FMGI_COLOUR_STATE_COUNT][3]) {
+    static_assert(FMGI_COLOUR_STATE_COUNT == FMGI_COLOUR_STATES && FMGI_COLOUR_STATE_COUNT == kRecolourStates &&
+                      FMGI_RECOLOUR_MAX_SCENARIOS == kRecolourMaxK, "one state count, one pass width");
+    if (!p || !table) return set_err(FMGI_ERR_ARG, "fmgi_palette_table: bad arguments");
+    if (!palette_ok(p))
+        return set_err(FMGI_ERR_ARG, "fmgi_palette_table: palette outside 0 <= window, light < 32, 0 <= floor_tint, albedo <= 1");
+    palette_fill(p, &table[0][0]);
+    return FMGI_OK;
+}
+
+FMGI_API size_t fmgi_states_bytes(int num_texels) {
+    return num_texels > 0 ? (size_t)FMGI_COLOUR_STATES * (size_t)num_texels * sizeof(unsigned long long) : 0;
+}
+
+FMGI_API int fmgi_bake_states(fmgi_context *c, uint64_t item_begin, uint64_t item_end, void *counts_dev, int kernel,
+                              void *stream) {
+    if (!c || !counts_dev) return set_err(FMGI_ERR_ARG, "fmgi_bake_states: bad arguments");
+    /* bake_common's AccState launch, counting into the caller's buffer: the context's own mode (and its
+       counters, if that mode is STATE) are put back untouched; the caller's memory is not under kStateBudget */
+    const int mode = c->accum;
+    c->accum = FMGI_ACCUM_STATE;
+    c->ext_counts = (unsigned long long *)counts_dev;
+    const int rc = bake_common(c, item_begin, item_end, counts_dev, kernel, stream ? (hipStream_t)stream : c->stream,
+                               false, nullptr, nullptr, nullptr);
+    c->ext_counts = nullptr;
+    c->accum = mode;
+    return rc;
+}
+
+FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
+                           int num_scenarios, void *const *lm_fx_dev, void *stream) {
+    if (!c || !counts_dev || !palettes || !lm_fx_dev || num_groups < 1 || num_scenarios < 1)
+        return set_err(FMGI_ERR_ARG, "fmgi_recolour: bad arguments");
+    const int G = num_groups, K = num_scenarios;
+    for (int g = 0; g < G; g++)
+        if (!counts_dev[g]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: histogram %d is NULL", g);
+    for (int k = 0; k < K; k++)
+        if (!lm_fx_dev[k]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: lightmap %d is NULL", k);
+    for (int64_t i = 0; i < (int64_t)K * G; i++)
+        if (!palette_ok(&palettes[i]))
+            return set_err(FMGI_ERR_ARG, "fmgi_recolour: palette of scenario %lld, group %lld outside 0 <= window, light "
+                                         "< 32, 0 <= floor_tint, albedo <= 1", (long long)(i / G), (long long)(i % G));
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_recolour: no scene");
+    /* one launch per pass (<= 8 scenarios) and group; its table: u32 [1024][k][3] */
+    struct Launch {
+        int k0, kn, g;
+        size_t off;
+    };
+    std::vector<Launch> launches;
+    std::vector<uint32_t> tab;
+    std::vector<int64_t> t64((size_t)FMGI_COLOUR_STATES * 3);
+    for (int k0 = 0; k0 < K; k0 += kRecolourMaxK) {
+        const int kn = std::min(kRecolourMaxK, K - k0);
+        for (int g = 0; g < G; g++) {
+            const size_t off = tab.size();
+            tab.resize(off + (size_t)FMGI_COLOUR_STATES * kn * 3);
+            bool any = false;
+            for (int k = 0; k < kn; k++) {
+                palette_fill(&palettes[(size_t)(k0 + k) * G + g], t64.data());
+                for (int s = 0; s < FMGI_COLOUR_STATES; s++)
+                    for (int ch = 0; ch < 3; ch++) {
+                        const int64_t v = t64[(size_t)3 * s + ch]; /* < 2^30 (palette_ok) */
+                        tab[off + ((size_t)s * kn + k) * 3 + ch] = (uint32_t)v;
+                        any |= v != 0;
+                    }
+            }
+            if (any)
+                launches.push_back({k0, kn, g, off});
+            else
+                tab.resize(off); /* switched off in every scenario of the pass: not read */
+        }
+    }
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot recolour");
+    if (launches.empty()) return FMGI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!c->ev_recolour) HIPCHK(hipEventCreateWithFlags(&c->ev_recolour, hipEventDisableTiming));
+    if (c->recolour_pending) { /* the previous call's launches still read the tables */
+        HIPCHK(hipEventSynchronize(c->ev_recolour));
+        c->recolour_pending = false;
+    }
+    if (c->recolour_tab_cap < tab.size()) {
+        hipFree(c->d_recolour_tab);
+        c->d_recolour_tab = nullptr;
+        c->recolour_tab_cap = 0;
+        HIPCHK(hipMalloc(&c->d_recolour_tab, tab.size() * sizeof(uint32_t)));
+        c->recolour_tab_cap = tab.size();
+    }
+    c->h_recolour_tab.swap(tab);
+    HIPCHK(hipMemcpyAsync(c->d_recolour_tab, c->h_recolour_tab.data(), c->h_recolour_tab.size() * sizeof(uint32_t),
+                          hipMemcpyHostToDevice, s));
+    c->recolour_pending = true; /* (set before the launches: an error below must not free tables in use) */
+    const int slabs = fmgi_recolour_slabs(c->num_texels, c->num_cus);
+    hipError_t err = hipSuccess;
+    for (const Launch &L : launches) {
+        RecolourArgs a;
+        memset(&a, 0, sizeof a);
+        a.counts = (const unsigned long long *)counts_dev[L.g];
+        a.table = c->d_recolour_tab + L.off;
+        for (int k = 0; k < L.kn; k++) a.lm[k] = (unsigned long long *)lm_fx_dev[L.k0 + k];
+        a.num_texels = c->num_texels;
+        a.k = L.kn;
+        a.slabs = slabs;
+        err = fmgi_launch_recolour(a, s);
+        if (err != hipSuccess) break;
+    }
+    const hipError_t ev = hipEventRecord(c->ev_recolour, s);
+    if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_recolour: %s", hipGetErrorString(err));
+    HIPCHK(ev);
+    return FMGI_OK;
 }
 
 FMGI_API int fmgi_finalize(fmgi_context *c, const void *lm, const void *tin, void *tout, void *stream) {

@@ -21,6 +21,7 @@ from . import scene
 
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
+                   COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette,
                    VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
@@ -60,6 +61,11 @@ __all__ = [
     "shade_views",
     "view_candidates",
     "view_stats",
+    "Palette",
+    "palette_table",
+    "states_bytes",
+    "COLOUR_STATE_COUNT",
+    "RECOLOUR_MAX_SCENARIOS",
 ]
 
 
@@ -86,6 +92,19 @@ def host_sincosf(x):
     c = np.empty_like(x)
     load().fmgi_host_sincosf(_ptr(x), _ptr(s), _ptr(c), len(x))
     return s, c
+
+
+def palette_table(p: Palette) -> np.ndarray:
+    """fmgi_palette_table: the deposit of every colour state under palette p, int64 [1024, 3] in units of
+    2^-25 (host only). Raises FmgiError for a palette outside the ranges."""
+    out = np.zeros((COLOUR_STATE_COUNT, 3), np.int64)
+    check(load().fmgi_palette_table(C.byref(p), _ptr(out)), "fmgi_palette_table")
+    return out
+
+
+def states_bytes(num_texels: int) -> int:
+    """Bytes of one histogram, uint64 [1024][num_texels] (fmgi_states_bytes)."""
+    return int(load().fmgi_states_bytes(int(num_texels)))
 
 
 def plan_count(sc: Scene, spa: int, wg: int = 256):
@@ -161,6 +180,43 @@ class Context:
         the context's internal stream, which is NOT ordered with torch's default stream."""
         check(self.lib.fmgi_bake_items(self.h, begin, end, C.c_void_p(lm_fx_ptr), kernel, C.c_void_p(stream or None)),
               "fmgi_bake_items")
+
+    def bake_states(self, begin: int, end: int, counts_ptr: int, kernel: int = KERNEL_AUTO, stream: int = 0):
+        """fmgi_bake_states: trace items [begin, end) like bake_items, counting every deposit in the device
+        histogram uint64 [1024][num_texels] at counts_ptr (states_bytes(num_texels) bytes; counts add to what it
+        holds). The context's accumulation mode is left as it is."""
+        check(self.lib.fmgi_bake_states(self.h, begin, end, C.c_void_p(counts_ptr), kernel, C.c_void_p(stream or None)),
+              "fmgi_bake_states")
+
+    def recolour(self, counts_ptrs, palettes, lm_ptrs, stream: int = 0):
+        """fmgi_recolour: lm[k] += the histograms counts_ptrs[g] folded with palettes[k][g], exactly, for every
+        scenario k (palettes: one row of len(counts_ptrs) Palette objects per scenario; lm_ptrs: one device
+        lightmap int64 [num_texels][4] per scenario). Asynchronous on `stream`."""
+        G, K = len(counts_ptrs), len(lm_ptrs)
+        if len(palettes) != K or any(len(row) != G for row in palettes):
+            raise FmgiError(f"recolour: palettes must be {K} scenarios x {G} groups")
+        cp = (C.c_void_p * max(G, 1))(*[C.c_void_p(int(p)) for p in counts_ptrs])
+        lp = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p)) for p in lm_ptrs])
+        pal = (Palette * max(K * G, 1))()
+        for k, row in enumerate(palettes):
+            for g, p in enumerate(row):
+                C.memmove(C.byref(pal, (k * G + g) * C.sizeof(Palette)), C.byref(p), C.sizeof(Palette))
+        check(self.lib.fmgi_recolour(self.h, cp, G, pal, K, lp, C.c_void_p(stream or None)), "fmgi_recolour")
+
+    def source_ranges(self):
+        """One (source, is_window, item_begin, item_end) per emitter of the planned schedule, windows first: the
+        item ranges that cut a bake into per-source histograms (bake_states)."""
+        out = []
+        for L in self.get_plan():
+            b, e = int(L["item_begin"]), int(L["item_begin"]) + int(L["count"])
+            src, win = int(L["source"]), int(L["is_window"])
+            if out and out[-1][0] == src:
+                assert out[-1][3] == b, f"source {src}: launches not contiguous"
+                out[-1] = (src, win, out[-1][2], e)
+            else:
+                assert src not in [o[0] for o in out], f"source {src}: launches not contiguous"
+                out.append((src, win, b, e))
+        return out
 
     def finalize(self, lm_fx_ptr: int, texels_in_ptr: int, texels_out_ptr: int, stream: int = 0):
         check(

@@ -69,6 +69,11 @@ EXPORTS = (
     "fmgi_view_candidates",
     "fmgi_view_stats",
     "fmgi_shade_views",
+    "fmgi_palette_reference",
+    "fmgi_palette_table",
+    "fmgi_states_bytes",
+    "fmgi_bake_states",
+    "fmgi_recolour",
 )
 
 KERNEL_EXACT = 0
@@ -84,6 +89,8 @@ ACCUM_STREAM = 4
 VIEW_NEAREST = 0
 VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
+COLOUR_STATE_COUNT = 1024
+RECOLOUR_MAX_SCENARIOS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
            "no_axes": 7}
@@ -156,6 +163,41 @@ class ViewStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+class Palette(C.Structure):
+    """fmgi_palette (include/flatmatch_gi.h): the colours a bake's histogram is folded with. Palette() is the
+    reference's (photonmap.cl:167-169, 241-249); keywords replace single constants, e.g.
+    Palette(light_rgb=(0, 0, 0)) switches the lamps off."""
+
+    _fields_ = [
+        ("window_rgb", C.c_float * 3),
+        ("light_rgb", C.c_float * 3),
+        ("floor_tint", C.c_float * 3),
+        ("albedo", C.c_float),
+    ]
+
+    def __init__(self, window_rgb=(18, 18, 18), light_rgb=(16, 16, 18), floor_tint=(1.0, 0.85, 0.7), albedo=0.9):
+        super().__init__()
+        for name, v in (("window_rgb", window_rgb), ("light_rgb", light_rgb), ("floor_tint", floor_tint)):
+            v = tuple(float(x) for x in v)
+            if len(v) != 3:
+                raise ValueError(f"{name}: three channels")
+            setattr(self, name, (C.c_float * 3)(*v))
+        self.albedo = float(albedo)
+
+    @classmethod
+    def reference(cls) -> "Palette":
+        p = cls()
+        load().fmgi_palette_reference(C.byref(p))
+        return p
+
+    def as_dict(self):
+        return {"window_rgb": list(self.window_rgb), "light_rgb": list(self.light_rgb),
+                "floor_tint": list(self.floor_tint), "albedo": float(self.albedo)}
+
+
+assert C.sizeof(Palette) == 40
 
 
 class Geometry(C.Structure):
@@ -249,6 +291,11 @@ def load() -> C.CDLL:
         "fmgi_view_candidates": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "fmgi_view_stats": (C.c_int, [C.POINTER(ViewStats)]),
         "fmgi_shade_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+        "fmgi_palette_reference": (None, [C.POINTER(Palette)]),
+        "fmgi_palette_table": (C.c_int, [C.POINTER(Palette), vp]),
+        "fmgi_states_bytes": (C.c_size_t, [C.c_int]),
+        "fmgi_bake_states": (C.c_int, [vp, u64, u64, vp, C.c_int, vp]),
+        "fmgi_recolour": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),
         "fmgi_filter_copy": (C.c_int, [vp, vp, vp, vp]),

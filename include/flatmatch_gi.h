@@ -299,6 +299,50 @@ int fmgi_bake_items(fmgi_context *ctx, uint64_t item_begin, uint64_t item_end, v
    .s[3] copied. Either texel pointer may alias. */
 int fmgi_finalize(fmgi_context *ctx, const void *lm_fx_dev, const void *texels_in_dev, void *texels_out_dev,
                   void *stream);
+/* ---- Recolouring a bake: per-state photon histograms ------------------------------ */
+/* A photon's path never depends on its colour, and the colour it deposits is a pure function of its 10-bit
+   colour state: bit 9 = the source kind (1: window, 0: light); below the leading 1 of bits 0-8, one bit per
+   diffuse bounce, oldest first, set when that bounce was on the floor. fmgi_bake_states keeps the bake's
+   deposit counts per (state, texel); fmgi_recolour folds such histograms with the tables of any palettes.
+   The int64 lightmap is then what fmgi_bake_items would give had photonmap.cl's constants been the
+   palette's, bit for bit; histograms of disjoint item ranges (one lamp, all windows, ...) add up to the whole
+   bake, so every group of sources takes its own palette (dimmed, switched off) per scenario. */
+#define FMGI_COLOUR_STATE_COUNT 1024
+#define FMGI_RECOLOUR_MAX_SCENARIOS 8 /* scenarios one kernel pass carries; fmgi_recolour takes any number */
+typedef struct fmgi_palette {          /* photonmap.cl:167-169, 241-249 */
+    float window_rgb[3], light_rgb[3]; /* 18,18,18 / 16,16,18 */
+    float floor_tint[3];               /* 1, 0.85, 0.7 */
+    float albedo;                      /* 0.9 */
+} fmgi_palette;
+/* photonmap.cl's constants */
+void fmgi_palette_reference(fmgi_palette *p);
+/* Host only: the deposit of every colour state in fixed point (units of 2^-25). Per state the kernel's float
+   operations in the kernel's order: start from the kind's colour; for every diffuse-bounce bit from the top,
+   multiply the three channels by floor_tint if the bit is set, then by albedo; each channel is then
+   (int64)ldexp(c, 25) (this truncation defines a deposit under a palette). Rows 0 and 512 (no leading 1) are
+   zero. FMGI_ERR_ARG unless every component is finite, 0 <= window_rgb, light_rgb < 32, 0 <= floor_tint <= 1
+   and 0 <= albedo <= 1; every value then lies in [0, 2^30). */
+int fmgi_palette_table(const fmgi_palette *p, int64_t table[FMGI_COLOUR_STATE_COUNT][3]);
+/* Bytes of one histogram, uint64 [FMGI_COLOUR_STATE_COUNT][num_texels]: 8 KiB per texel (0 if num_texels < 1). */
+size_t fmgi_states_bytes(int num_texels);
+/* fmgi_bake_items' trace of work items [item_begin, item_end), counting every deposit in the caller's device
+   histogram counts_dev[state][texel] (fmgi_states_bytes(numTexels) bytes) with one 64-bit device atomic each.
+   Nothing is folded or zeroed: counts add to what the buffer holds, so several ranges or calls accumulate.
+   Works whatever fmgi_set_accumulation selected, and leaves that mode as it is. Asynchronous on `stream`. */
+int fmgi_bake_states(fmgi_context *ctx, uint64_t item_begin, uint64_t item_end, void *counts_dev, int kernel,
+                     void *stream);
+/* For every scenario k and texel t:
+     lm_fx[k][t][c] += sum over groups g and states s of counts[g][s][t] * table(palettes[k * num_groups + g])[s][c]
+   in exact 64-bit integers (mod 2^64). counts_dev[num_groups] = device histograms of the current scene's texel
+   count (read only); lm_fx_dev[num_scenarios] = distinct device lightmaps (int64 [numTexels][4]; .s[3] is not
+   touched). Asynchronous on `stream`; the palettes are read before the call returns. The tables are built and
+   every argument is checked on the host before any device call: FMGI_ERR_ARG for num_groups < 1,
+   num_scenarios < 1, a NULL pointer or a palette fmgi_palette_table rejects, FMGI_ERR_STATE without a scene,
+   then FMGI_ERR_NO_DEVICE on a host-only context. A group whose table is zero in every scenario of a pass (a
+   lamp switched off) is not read. */
+int fmgi_recolour(fmgi_context *ctx, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
+                  int num_scenarios, void *const *lm_fx_dev, void *stream);
+
 /* The kernel FMGI_KERNEL_AUTO resolves to for the current scene. */
 int fmgi_auto_kernel(const fmgi_context *ctx);
 /* The profiler's name of the k_bake instance the last bake launch ran ("void (anonymous namespace)::k_bake<...>

@@ -1,0 +1,173 @@
+#!/usr/bin/env python
+"""Bake a scene once, then light it as often as wanted: per-state photon histograms.
+
+The scene (a FMGIGEO1 geometry fixture, or box8 / box200 / box2000 with --tile-size / --with-light) is traced
+once into one histogram per group of sources: all windows together, and the lights together or, with
+--per-light, one group each. Every scenario of the JSON file then costs one pass over the histograms
+(fmgi.Context.recolour) instead of a bake: the lightmap is exactly what a bake with the scenario's colours in
+place of photonmap.cl's constants would give. Each result is finalised, normalised and turned into the walls'
+RGB8 tiles (fmgi.output_tiles), and written to OUT/<name>/texels.npy (float32 [numTexels, 4], normalised) and
+OUT/<name>/tiles.npy (uint8). With --view a camera picture (fmgi.shade_views) goes to OUT/<name>/view.ppm.
+
+The scenario file is a JSON list; every entry has a name and a palette per group:
+
+  [{"name": "day"},
+   {"name": "evening", "windows": {"window_rgb": [4, 3, 6]}, "lights": {"light_rgb": [20, 16, 9]}},
+   {"name": "night",   "windows": {"off": true}, "lights": [{"scale": 0.5}, {"off": true}]}]
+
+A palette may set window_rgb, light_rgb, floor_tint, albedo (defaults: the reference's 18,18,18 / 16,16,18 /
+1,0.85,0.7 / 0.9), "scale" (multiplies both emitter colours) or "off" (emitters 0). "lights" is one palette for
+every light group, or with --per-light a list with one palette per light. A histogram takes 8 KiB per texel and
+group of device memory.
+
+  python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --scenarios scenarios.json -o out
+"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd"), os.path.join(REPO, "tools")]
+
+import numpy as np  # noqa: E402
+
+
+def load_scene(name, tile_size, with_light):
+    from fmgi import scene
+
+    if name.startswith("box") and name[3:].isdigit():
+        kw = {} if tile_size is None else {"tile_size": tile_size}
+        return scene.box_scene(int(name[3:]), with_light=with_light, **kw)
+    return scene.load_geometry(name)
+
+
+def palette_of(spec):
+    """A fmgi.Palette from a scenario file's palette object."""
+    import fmgi
+
+    spec = dict(spec or {})
+    off, scale = bool(spec.pop("off", False)), float(spec.pop("scale", 1.0))
+    unknown = set(spec) - {"window_rgb", "light_rgb", "floor_tint", "albedo"}
+    if unknown:
+        raise SystemExit(f"palette keys {sorted(unknown)}: window_rgb, light_rgb, floor_tint, albedo, scale or off")
+    p = fmgi.Palette(**spec)
+    if off or scale != 1.0:
+        k = 0.0 if off else scale
+        p = fmgi.Palette(window_rgb=[k * v for v in p.window_rgb], light_rgb=[k * v for v in p.light_rgb],
+                         floor_tint=list(p.floor_tint), albedo=p.albedo)
+    return p
+
+
+def source_groups(ranges, per_light):
+    """[(label, item_begin, item_end, is_window)]: the windows, then the lights (together, or one group each)."""
+    win = [r for r in ranges if r[1]]
+    lights = [r for r in ranges if not r[1]]
+    groups = []
+    if win:
+        groups.append(("windows", win[0][2], win[-1][3], True))
+    if lights and per_light:
+        groups += [(f"light{k}", r[2], r[3], False) for k, r in enumerate(lights)]
+    elif lights:
+        groups.append(("lights", lights[0][2], lights[-1][3], False))
+    return groups
+
+
+def scenario_palettes(entry, groups):
+    """One palette per group for a scenario entry."""
+    lights = entry.get("lights")
+    n_light = sum(1 for g in groups if not g[3])
+    if isinstance(lights, list):
+        if len(lights) != n_light:
+            raise SystemExit(f"scenario {entry['name']!r}: {len(lights)} light palettes for {n_light} light groups")
+        per = list(lights)
+    else:
+        per = [lights] * n_light
+    row, k = [], 0
+    for g in groups:
+        if g[3]:
+            row.append(palette_of(entry.get("windows")))
+        else:
+            row.append(palette_of(per[k]))
+            k += 1
+    return row
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
+    ap.add_argument("--tile-size", type=float, default=None, help="box scenes: lightmap texels per m^2 (default 200)")
+    ap.add_argument("--with-light", action="store_true", help="box scenes: add the ceiling light")
+    ap.add_argument("--spa", type=int, required=True, help="numSamplesPerArea of the bake")
+    ap.add_argument("--scenarios", required=True, help="JSON file: a list of {name, windows, lights}")
+    ap.add_argument("--per-light", action="store_true", help="one histogram per light instead of one for all")
+    ap.add_argument("--offsets", default=None, help=".npy of int32 launch offsets (default: libc rand(), as the reference)")
+    ap.add_argument("--kernel", choices=("auto", "exact", "fast", "grid", "hybrid"), default="auto")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("-o", "--output", default="out")
+    ap.add_argument("--view", action="store_true", help="also write OUT/<name>/view.ppm")
+    ap.add_argument("--pos", type=float, nargs=3, default=(5, 5.2, 1.6))
+    ap.add_argument("--dir", type=float, nargs=3, default=(1, 1, 0))
+    ap.add_argument("--up", type=float, nargs=3, default=(0, 0, 1))
+    ap.add_argument("--pixel", type=float, default=0.001)
+    ap.add_argument("--width", type=int, default=1024)
+    ap.add_argument("--height", type=int, default=768)
+    ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
+    ap.add_argument("--samples", type=int, default=2, help="N x N rays per pixel (1..8)")
+    ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
+    a = ap.parse_args(argv)
+    import torch
+
+    import fmgi
+
+    with open(a.scenarios) as f:
+        entries = json.load(f)
+    if not isinstance(entries, list) or not entries or any("name" not in e for e in entries):
+        sys.exit(f"{a.scenarios}: a non-empty JSON list of objects with a name")
+    names = [str(e["name"]) for e in entries]
+    if len(set(names)) != len(names) or any(os.sep in n or n in ("", ".", "..") for n in names):
+        sys.exit(f"{a.scenarios}: scenario names must be distinct directory names")
+    sc = load_scene(a.scene, a.tile_size, a.with_light)
+    dev = f"cuda:{a.device}"
+    ctx = fmgi.Context(a.device)
+    ctx.set_scene(sc)
+    items = ctx.plan(a.spa, rng_offsets=None if a.offsets is None else np.load(a.offsets))
+    groups = source_groups(ctx.source_ranges(), a.per_light)
+    if not groups:
+        sys.exit("the scene has no windows and no lights")
+    palettes = [scenario_palettes(e, groups) for e in entries]
+    kernel = {"auto": fmgi.KERNEL_AUTO, "exact": fmgi.KERNEL_EXACT, "fast": fmgi.KERNEL_FAST,
+              "grid": fmgi.KERNEL_GRID, "hybrid": fmgi.KERNEL_HYBRID}[a.kernel]
+    T = sc.num_texels
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        hists = [torch.zeros((fmgi.COLOUR_STATE_COUNT, T), dtype=torch.int64, device=dev) for _ in groups]
+        for h, (_, b, e, _) in zip(hists, groups):
+            ctx.bake_states(b, e, h.data_ptr(), kernel, s.cuda_stream)
+        lms = [torch.zeros((T, 4), dtype=torch.int64, device=dev) for _ in entries]
+        ctx.recolour([h.data_ptr() for h in hists], palettes, [lm.data_ptr() for lm in lms], s.cuda_stream)
+        zero = torch.zeros((T, 4), dtype=torch.float32, device=dev)
+        texels = [torch.empty((T, 4), dtype=torch.float32, device=dev) for _ in entries]
+        for lm, t in zip(lms, texels):
+            ctx.finalize(lm.data_ptr(), zero.data_ptr(), t.data_ptr(), s.cuda_stream)
+    s.synchronize()
+    print(f"{sc.name}: {100 * items} photons, {T} texels, {len(groups)} histograms of "
+          f"{fmgi.states_bytes(T) / 2**20:.1f} MiB ({', '.join(g[0] for g in groups)}), {len(entries)} scenarios")
+    for name, t in zip(names, texels):
+        d = os.path.join(a.output, name)
+        os.makedirs(d, exist_ok=True)
+        tex, tiles = fmgi.output_tiles(sc, t.cpu().numpy(), a.spa)
+        np.save(os.path.join(d, "texels.npy"), tex)
+        np.save(os.path.join(d, "tiles.npy"), tiles)
+        if a.view:
+            from render_view import write_ppm
+
+            out = fmgi.shade_views(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, tiles,
+                                   tuple(a.background), samples=a.samples, filter=a.filter)
+            write_ppm(os.path.join(d, "view.ppm"), out["rgb"][0])
+        print(f"  {d}: mean texel {tex[:, :3].mean():.6g}")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
