@@ -32,6 +32,7 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_internal.h"
+#include "fmgi_filter.h"
 #include "fmgi_recolour.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
@@ -721,6 +722,20 @@ struct fmgi_context {
     std::vector<uint32_t> h_recolour_tab;
     hipEvent_t ev_recolour = nullptr;
     bool recolour_pending = false;
+    /* fmgi_filter_radii / fmgi_filter_apply: the walls' lightmapSetup {s0, s1, s2} (kept by
+       fmgi_set_scene), the texel / wall / column tables built from them on the first filter call of a scene, and
+       the prefix-sum scratch (u64 [planes][num_texels], grown on demand); a later call's stream waits for
+       ev_filter, recorded after a call's last launch, before it overwrites the scratch */
+    std::vector<int32_t> h_wall_lm;
+    FilterTex *d_filter_tex = nullptr;
+    FilterWall *d_filter_walls = nullptr;
+    FilterCol *d_filter_cols = nullptr;
+    int filter_cols = 0;
+    bool filter_ready = false; /* the tables are those of h_wall_lm and num_texels (fmgi_set_scene clears it) */
+    unsigned long long *d_filter_sat = nullptr;
+    size_t filter_sat_cap = 0;
+    hipEvent_t ev_filter = nullptr;
+    bool filter_pending = false;
     uint32_t *d_colpack = nullptr; /* the same table as u32 {r, g, b, 0} (STREAM fold) */
     /* STREAM: deposit-code stream + fold buffers, grown on demand (fmgi_accum.hip); two sets, so the
        fold of one chunk (on fold_stream) overlaps the bake of the next */
@@ -854,6 +869,11 @@ FMGI_API void fmgi_destroy(fmgi_context *c) {
     hipFree(c->d_colfx);
     if (c->ev_recolour) { hipEventSynchronize(c->ev_recolour); hipEventDestroy(c->ev_recolour); }
     hipFree(c->d_recolour_tab);
+    if (c->ev_filter) { hipEventSynchronize(c->ev_filter); hipEventDestroy(c->ev_filter); }
+    hipFree(c->d_filter_tex);
+    hipFree(c->d_filter_walls);
+    hipFree(c->d_filter_cols);
+    hipFree(c->d_filter_sat);
     if (c->fold_stream) hipStreamSynchronize(c->fold_stream);
     for (int k = 0; k < 2; k++) {
         hipFree(c->sb[k].stream);
@@ -1463,6 +1483,11 @@ FMGI_API int fmgi_set_scene(fmgi_context *c, const fmgi_rect *walls, int num_wal
     HIPCHK(upload(&c->d_gidx, gb.idx));
     }
     c->num_texels = num_texels;
+    /* the filter's grids change with the texel count, also when a step below fails: its tables are rebuilt */
+    c->h_wall_lm.resize((size_t)num_walls * 3);
+    for (int i = 0; i < num_walls; i++)
+        for (int k = 0; k < 3; k++) c->h_wall_lm[(size_t)3 * i + k] = walls[i].lightmapSetup[k];
+    c->filter_ready = false;
     if (c->device != FMGI_HOST_ONLY) {
         int rc = configure_accum(c);
         if (rc != FMGI_OK) return rc;
@@ -2569,6 +2594,134 @@ FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int n
     }
     const hipError_t ev = hipEventRecord(c->ev_recolour, s);
     if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_recolour: %s", hipGetErrorString(err));
+    HIPCHK(ev);
+    return FMGI_OK;
+}
+
+/* ---- adaptive density filter ---- */
+
+FMGI_API uint64_t fmgi_filter_energy(const fmgi_palette *p, uint64_t deposits) {
+    fmgi_palette ref;
+    if (!p) {
+        fmgi_palette_reference(&ref);
+        p = &ref;
+    }
+    if (!palette_ok(p)) {
+        set_err(FMGI_ERR_ARG, "fmgi_filter_energy: palette outside 0 <= window, light < 32, 0 <= floor_tint, albedo <= 1");
+        return 0;
+    }
+    uint64_t sum = 0; /* a first-bounce window photon's deposit: colour state 512 | 1 of fmgi_palette_table */
+    for (int k = 0; k < 3; k++) sum += (uint64_t)(int64_t)ldexp((double)p->window_rgb[k], FMGI_FX_SHIFT);
+    return deposits * sum;
+}
+
+/* The scene's texel / wall / column tables and a scratch of `planes` planes on the device; then s waits for the
+   previous filter call's launches (they read and wrote the scratch). Tables and scratch are replaced only here,
+   through hipFree, which waits for the device. */
+static int filter_prepare(fmgi_context *c, int planes, hipStream_t s) {
+    const size_t T = (size_t)c->num_texels;
+    if (!c->filter_ready) {
+        const int nw = (int)(c->h_wall_lm.size() / 3);
+        std::vector<FilterTex> tex(T, FilterTex{-1, 0});
+        std::vector<FilterWall> walls((size_t)std::max(nw, 1), FilterWall{0, 1, 1, 0});
+        std::vector<FilterCol> cols;
+        for (int i = 0; i < nw; i++) {
+            const int32_t *lm = &c->h_wall_lm[(size_t)3 * i]; /* inside [0, T): checked by fmgi_set_scene */
+            walls[(size_t)i] = FilterWall{lm[0], lm[1], lm[2], 0};
+            for (int y = 0; y < lm[2]; y++)
+                for (int x = 0; x < lm[1]; x++) tex[(size_t)lm[0] + (size_t)y * lm[1] + x] = FilterTex{i, y};
+            for (int x = 0; x < lm[1]; x++) cols.push_back(FilterCol{i, x});
+        }
+        hipFree(c->d_filter_tex);
+        hipFree(c->d_filter_walls);
+        hipFree(c->d_filter_cols);
+        c->d_filter_tex = nullptr;
+        c->d_filter_walls = nullptr;
+        c->d_filter_cols = nullptr;
+        c->filter_cols = 0;
+        HIPCHK(upload(&c->d_filter_tex, tex));
+        HIPCHK(upload(&c->d_filter_walls, walls));
+        if (!cols.empty()) HIPCHK(upload(&c->d_filter_cols, cols));
+        c->filter_cols = (int)cols.size();
+        c->filter_ready = true;
+    }
+    if (c->filter_sat_cap < (size_t)planes * T) {
+        hipFree(c->d_filter_sat);
+        c->d_filter_sat = nullptr;
+        c->filter_sat_cap = 0;
+        HIPCHK(hipMalloc(&c->d_filter_sat, (size_t)planes * T * sizeof(unsigned long long)));
+        c->filter_sat_cap = (size_t)planes * T;
+    }
+    if (!c->ev_filter) HIPCHK(hipEventCreateWithFlags(&c->ev_filter, hipEventDisableTiming));
+    if (c->filter_pending) HIPCHK(hipStreamWaitEvent(s, c->ev_filter, 0));
+    return FMGI_OK;
+}
+
+static FilterArgs filter_args(const fmgi_context *c) {
+    FilterArgs a;
+    memset(&a, 0, sizeof a);
+    a.tex = c->d_filter_tex;
+    a.walls = c->d_filter_walls;
+    a.cols = c->d_filter_cols;
+    a.num_texels = c->num_texels;
+    a.num_cols = c->filter_cols;
+    a.sat = c->d_filter_sat;
+    return a;
+}
+
+FMGI_API int fmgi_filter_radii(fmgi_context *c, const void *guide_lm_fx_dev, uint64_t min_energy, int max_radius,
+                               void *radii_dev, void *stream) {
+    static_assert(FMGI_FILTER_MAX_RADIUS == kFilterMaxRadius && FMGI_FILTER_MAX_MAPS == kFilterMaxMaps,
+                  "one radius limit, one pass width");
+    if (!c || !guide_lm_fx_dev || !radii_dev || max_radius < 0 || max_radius > FMGI_FILTER_MAX_RADIUS)
+        return set_err(FMGI_ERR_ARG, "fmgi_filter_radii: bad arguments (max_radius 0..%d)", FMGI_FILTER_MAX_RADIUS);
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_filter_radii: no scene");
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot filter");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int rc = filter_prepare(c, 1, s);
+    if (rc != FMGI_OK) return rc;
+    FilterArgs a = filter_args(c);
+    a.guide = (const unsigned long long *)guide_lm_fx_dev;
+    a.radii_out = (uint8_t *)radii_dev;
+    a.min_energy = min_energy;
+    a.max_radius = max_radius;
+    c->filter_pending = true;
+    hipError_t err = fmgi_launch_filter_sat(a, 1, s);
+    if (err == hipSuccess) err = fmgi_launch_filter_radii(a, s);
+    const hipError_t ev = hipEventRecord(c->ev_filter, s);
+    if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_filter_radii: %s", hipGetErrorString(err));
+    HIPCHK(ev);
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_filter_apply(fmgi_context *c, const void *radii_dev, const void *const *lm_in_dev,
+                               void *const *lm_out_dev, int num_maps, void *stream) {
+    if (!c || !radii_dev || !lm_in_dev || !lm_out_dev || num_maps < 1)
+        return set_err(FMGI_ERR_ARG, "fmgi_filter_apply: bad arguments");
+    for (int k = 0; k < num_maps; k++)
+        if (!lm_in_dev[k] || !lm_out_dev[k]) return set_err(FMGI_ERR_ARG, "fmgi_filter_apply: map %d is NULL", k);
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_filter_apply: no scene");
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot filter");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int rc = filter_prepare(c, 3 * std::min(num_maps, kFilterMaxMaps), s);
+    if (rc != FMGI_OK) return rc;
+    c->filter_pending = true;
+    hipError_t err = hipSuccess;
+    for (int k0 = 0; k0 < num_maps && err == hipSuccess; k0 += kFilterMaxMaps) { /* a pass: <= 8 maps */
+        FilterArgs a = filter_args(c);
+        a.maps = std::min(kFilterMaxMaps, num_maps - k0);
+        for (int k = 0; k < a.maps; k++) {
+            a.in[k] = (const unsigned long long *)lm_in_dev[k0 + k];
+            a.out[k] = (unsigned long long *)lm_out_dev[k0 + k];
+        }
+        a.radii_in = (const uint8_t *)radii_dev;
+        err = fmgi_launch_filter_sat(a, 3 * a.maps, s);
+        if (err == hipSuccess) err = fmgi_launch_filter_apply(a, s);
+    }
+    const hipError_t ev = hipEventRecord(c->ev_filter, s);
+    if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_filter_apply: %s", hipGetErrorString(err));
     HIPCHK(ev);
     return FMGI_OK;
 }

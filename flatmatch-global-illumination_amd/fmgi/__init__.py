@@ -21,7 +21,7 @@ from . import scene
 
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
-                   COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette,
+                   COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
                    VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
@@ -66,6 +66,10 @@ __all__ = [
     "states_bytes",
     "COLOUR_STATE_COUNT",
     "RECOLOUR_MAX_SCENARIOS",
+    "FILTER_MAX_RADIUS",
+    "FILTER_MAX_MAPS",
+    "filter_energy",
+    "filter_lightmap",
 ]
 
 
@@ -105,6 +109,50 @@ def palette_table(p: Palette) -> np.ndarray:
 def states_bytes(num_texels: int) -> int:
     """Bytes of one histogram, uint64 [1024][num_texels] (fmgi_states_bytes)."""
     return int(load().fmgi_states_bytes(int(num_texels)))
+
+
+def filter_energy(deposits: int, palette: Palette | None = None) -> int:
+    """fmgi_filter_energy: the min_energy that stands for `deposits` first-bounce window photons under `palette`
+    (None: the reference's), in units of 2^-25, mod 2^64 (host only)."""
+    if palette is not None:
+        palette_table(palette)  # raises FmgiError for a palette outside the ranges
+    p = None if palette is None else C.byref(palette)
+    return int(load().fmgi_filter_energy(p, int(deposits) & ((1 << 64) - 1)))
+
+
+def filter_lightmap(sc: Scene, lm_fx: np.ndarray, min_deposits: int, max_radius: int = 4,
+                    guide: np.ndarray | None = None, device: int = 0):
+    """The adaptive density filter on host arrays (fmgi_filter_radii + fmgi_filter_apply on `device`): lm_fx is an
+    int64 lightmap [numTexels, 3 or 4]; the radii come from `guide` (default: lm_fx itself) at min_energy =
+    filter_energy(min_deposits). Returns (out, radii): out like lm_fx, radii uint8 [numTexels]."""
+    import torch
+
+    def four(a, what):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[0] != sc.num_texels or a.shape[1] not in (3, 4) or a.dtype != np.int64:
+            raise FmgiError(f"filter_lightmap: {what} {a.shape} {a.dtype}, need int64 [{sc.num_texels}, 3 or 4]")
+        out = np.zeros((sc.num_texels, 4), np.int64)
+        out[:, : a.shape[1]] = a
+        return out
+
+    lm = four(lm_fx, "lm_fx")
+    g = lm if guide is None else four(guide, "guide")
+    dev = f"cuda:{device}"
+    ctx = Context(device)
+    try:
+        ctx.set_scene(sc)
+        s = torch.cuda.Stream(device=dev)
+        with torch.cuda.stream(s):
+            d_guide, d_lm = torch.from_numpy(g).to(dev), torch.from_numpy(lm).to(dev)
+            d_radii = torch.zeros(sc.num_texels, dtype=torch.uint8, device=dev)
+            ctx.filter_radii(d_guide.data_ptr(), filter_energy(min_deposits), max_radius, d_radii.data_ptr(),
+                             s.cuda_stream)
+            ctx.filter_apply(d_radii.data_ptr(), [d_lm.data_ptr()], [d_lm.data_ptr()], s.cuda_stream)
+        s.synchronize()
+        out, radii = d_lm.cpu().numpy()[:, : np.shape(lm_fx)[1]], d_radii.cpu().numpy()
+    finally:
+        ctx.close()
+    return out, radii
 
 
 def plan_count(sc: Scene, spa: int, wg: int = 256):
@@ -202,6 +250,27 @@ class Context:
             for g, p in enumerate(row):
                 C.memmove(C.byref(pal, (k * G + g) * C.sizeof(Palette)), C.byref(p), C.sizeof(Palette))
         check(self.lib.fmgi_recolour(self.h, cp, G, pal, K, lp, C.c_void_p(stream or None)), "fmgi_recolour")
+
+    def filter_radii(self, guide_ptr: int, min_energy: int, max_radius: int, radii_ptr: int, stream: int = 0):
+        """fmgi_filter_radii: per level-0 texel the smallest window radius in [0, max_radius] that holds
+        min_energy (unsigned, units of 2^-25; see filter_energy) of the device guide lightmap int64
+        [num_texels][4] at guide_ptr, into the device array uint8 [num_texels] at radii_ptr. Asynchronous on
+        `stream`."""
+        check(self.lib.fmgi_filter_radii(self.h, C.c_void_p(guide_ptr or None), int(min_energy) & ((1 << 64) - 1),
+                                         int(max_radius), C.c_void_p(radii_ptr or None), C.c_void_p(stream or None)),
+              "fmgi_filter_radii")
+
+    def filter_apply(self, radii_ptr: int, in_ptrs, out_ptrs, stream: int = 0):
+        """fmgi_filter_apply: out_ptrs[k] = the device lightmap in_ptrs[k] (int64 [num_texels][4]) averaged over
+        every level-0 texel's window of the radii at radii_ptr, exactly; out_ptrs[k] may be in_ptrs[k].
+        Asynchronous on `stream`."""
+        K = len(in_ptrs)
+        if len(out_ptrs) != K:
+            raise FmgiError(f"filter_apply: {K} inputs, {len(out_ptrs)} outputs")
+        ip = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p) or None) for p in in_ptrs])
+        op = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p) or None) for p in out_ptrs])
+        check(self.lib.fmgi_filter_apply(self.h, C.c_void_p(radii_ptr or None), ip, op, K, C.c_void_p(stream or None)),
+              "fmgi_filter_apply")
 
     def source_ranges(self):
         """One (source, is_window, item_begin, item_end) per emitter of the planned schedule, windows first: the

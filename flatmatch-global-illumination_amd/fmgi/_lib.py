@@ -74,6 +74,9 @@ EXPORTS = (
     "fmgi_states_bytes",
     "fmgi_bake_states",
     "fmgi_recolour",
+    "fmgi_filter_energy",
+    "fmgi_filter_radii",
+    "fmgi_filter_apply",
 )
 
 KERNEL_EXACT = 0
@@ -91,6 +94,8 @@ VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
 COLOUR_STATE_COUNT = 1024
 RECOLOUR_MAX_SCENARIOS = 8
+FILTER_MAX_RADIUS = 16
+FILTER_MAX_MAPS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
            "no_axes": 7}
@@ -296,6 +301,9 @@ def load() -> C.CDLL:
         "fmgi_states_bytes": (C.c_size_t, [C.c_int]),
         "fmgi_bake_states": (C.c_int, [vp, u64, u64, vp, C.c_int, vp]),
         "fmgi_recolour": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+        "fmgi_filter_energy": (u64, [C.POINTER(Palette), u64]),
+        "fmgi_filter_radii": (C.c_int, [vp, vp, u64, C.c_int, vp, vp]),
+        "fmgi_filter_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),
         "fmgi_filter_copy": (C.c_int, [vp, vp, vp, vp]),

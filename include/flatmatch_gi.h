@@ -343,6 +343,40 @@ int fmgi_bake_states(fmgi_context *ctx, uint64_t item_begin, uint64_t item_end, 
 int fmgi_recolour(fmgi_context *ctx, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
                   int num_scenarios, void *const *lm_fx_dev, void *stream);
 
+/* ---- Adaptive density filter for noisy, low-photon lightmaps ------------------------ */
+/* A radiance estimate on the binned photons: per level-0 texel a square window, grown until it holds enough
+   deposit energy and clipped to the texel's own wall, then the mean over that window. No reference counterpart.
+   All values are unsigned 64-bit integers mod 2^64, so the result is exact and independent of any order.
+   Wall w's level-0 grid is texel (x, y) = s0 + y * s1 + x, 0 <= x < s1, 0 <= y < s2 (lightmapSetup = {s0, s1,
+   s2, 0}); W_r(x, y) = [max(x - r, 0), min(x + r, s1 - 1)] x [max(y - r, 0), min(y + r, s2 - 1)] holds n_r texels.
+   It is a box estimate: it smooths across shadow edges inside a wall and never across walls. Level-0 ranges of
+   different walls that overlap give unspecified results. */
+#define FMGI_FILTER_MAX_RADIUS 16
+#define FMGI_FILTER_MAX_MAPS 8   /* maps one kernel pass carries; the call takes any number */
+/* deposits x the fixed-point sum of the palette's window colour (NULL: the reference's 18,18,18): the
+   min_energy that stands for `deposits` first-bounce window photons. Host only. 0 (and fmgi_last_error) for a
+   palette fmgi_palette_table rejects. */
+uint64_t fmgi_filter_energy(const fmgi_palette *p, uint64_t deposits);
+/* radii[t] = the smallest r in [0, max_radius] whose window holds S_r >= min_energy (compared unsigned), S_r the
+   sum over W_r of e = g[.][0] + g[.][1] + g[.][2] of the guide lightmap g (int64 [numTexels][4]); max_radius if
+   there is none; 0 for texels in no wall's level-0 grid (the mip levels). radii_dev: uint8 [numTexels]. */
+int fmgi_filter_radii(fmgi_context *ctx, const void *guide_lm_fx_dev, uint64_t min_energy, int max_radius,
+                      void *radii_dev /* uint8 [numTexels] */, void *stream);
+/* For every map k and level-0 texel t, with r = min(radii[t], 16): out[k][t][c] = (sum of in[k][.][c] over W_r) /
+   n_r (unsigned division) for c = 0..2 and out[k][t][3] = in[k][t][3]; every other texel is copied, all four
+   words. A window sum below 2^64 comes out exact whatever the lightmap's total. lm_out_dev[k] may be
+   lm_in_dev[k]; the maps must not overlap in any other way. radii of one guide serve any number of maps (all
+   scenarios of a relight session share the radii of the reference-palette lightmap of all sources); radii all 0
+   give out == in.
+   Both calls take device pointers of the current scene's texel count and are asynchronous on `stream`. Arguments
+   are checked on the host before any device call: FMGI_ERR_ARG for a NULL context or pointer, num_maps < 1 or
+   max_radius outside 0..FMGI_FILTER_MAX_RADIUS, then FMGI_ERR_STATE without a scene, then FMGI_ERR_NO_DEVICE on a
+   host-only context. The prefix sums the kernels work on live in scratch memory of the context (8 B per texel
+   for the radii, 24 B per texel and map of a pass), allocated on first use; a later call's stream waits for the
+   earlier call before it reuses them, without blocking the host. */
+int fmgi_filter_apply(fmgi_context *ctx, const void *radii_dev, const void *const *lm_in_dev,
+                      void *const *lm_out_dev, int num_maps, void *stream);
+
 /* The kernel FMGI_KERNEL_AUTO resolves to for the current scene. */
 int fmgi_auto_kernel(const fmgi_context *ctx);
 /* The profiler's name of the k_bake instance the last bake launch ran ("void (anonymous namespace)::k_bake<...>

@@ -20,7 +20,13 @@ A palette may set window_rgb, light_rgb, floor_tint, albedo (defaults: the refer
 every light group, or with --per-light a list with one palette per light. A histogram takes 8 KiB per texel and
 group of device memory.
 
+A bake of few photons is speckled; --min-deposits N smooths every scenario's lightmap with the adaptive density
+filter before it is finalised: per texel a window of radius <= --max-radius, grown until it
+holds the energy of N first-bounce window photons in the reference-palette lightmap of all groups, so all
+scenarios share one radius map.
+
   python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --scenarios scenarios.json -o out
+  python tools/relight.py tests/golden/example_geometry.bin --spa 65000 --min-deposits 256 --scenarios scenarios.json
 """
 import argparse
 import json
@@ -93,7 +99,7 @@ def scenario_palettes(entry, groups):
     return row
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
     ap.add_argument("--tile-size", type=float, default=None, help="box scenes: lightmap texels per m^2 (default 200)")
@@ -115,7 +121,20 @@ def main(argv=None):
     ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
     ap.add_argument("--samples", type=int, default=2, help="N x N rays per pixel (1..8)")
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
+    ap.add_argument("--min-deposits", type=int, default=0,
+                    help="adaptive density filter: grow every texel's window until it holds the energy of N "
+                         "first-bounce window photons (default 0: no filter)")
+    ap.add_argument("--max-radius", type=int, default=4, help="the filter's largest window radius in texels (0..16)")
     a = ap.parse_args(argv)
+    if a.min_deposits < 0:
+        ap.error("--min-deposits must not be negative")
+    if not 0 <= a.max_radius <= 16:
+        ap.error("--max-radius must be in 0..16")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
 
     import fmgi
@@ -146,6 +165,15 @@ def main(argv=None):
             ctx.bake_states(b, e, h.data_ptr(), kernel, s.cuda_stream)
         lms = [torch.zeros((T, 4), dtype=torch.int64, device=dev) for _ in entries]
         ctx.recolour([h.data_ptr() for h in hists], palettes, [lm.data_ptr() for lm in lms], s.cuda_stream)
+        if a.min_deposits > 0:
+            # one radius map for every scenario, from the photon density: the reference-palette lightmap of all groups
+            guide = torch.zeros((T, 4), dtype=torch.int64, device=dev)
+            ctx.recolour([h.data_ptr() for h in hists], [[fmgi.Palette()] * len(groups)], [guide.data_ptr()], s.cuda_stream)
+            radii = torch.zeros(T, dtype=torch.uint8, device=dev)
+            ctx.filter_radii(guide.data_ptr(), fmgi.filter_energy(a.min_deposits), a.max_radius, radii.data_ptr(),
+                             s.cuda_stream)
+            ptrs = [lm.data_ptr() for lm in lms]
+            ctx.filter_apply(radii.data_ptr(), ptrs, ptrs, s.cuda_stream)
         zero = torch.zeros((T, 4), dtype=torch.float32, device=dev)
         texels = [torch.empty((T, 4), dtype=torch.float32, device=dev) for _ in entries]
         for lm, t in zip(lms, texels):
@@ -153,6 +181,9 @@ def main(argv=None):
     s.synchronize()
     print(f"{sc.name}: {100 * items} photons, {T} texels, {len(groups)} histograms of "
           f"{fmgi.states_bytes(T) / 2**20:.1f} MiB ({', '.join(g[0] for g in groups)}), {len(entries)} scenarios")
+    if a.min_deposits > 0:
+        print(f"  filtered: {a.min_deposits} deposits, radius <= {a.max_radius}, mean radius "
+              f"{radii.float().mean().item():.3f}")
     for name, t in zip(names, texels):
         d = os.path.join(a.output, name)
         os.makedirs(d, exist_ok=True)
