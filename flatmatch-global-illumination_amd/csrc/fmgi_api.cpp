@@ -774,7 +774,7 @@ struct fmgi_context {
     std::string last_kernel; /* fmgi_last_bake_kernel: the instance(s) the last bake launch ran */
     int grid_cpr = 0; /* fmgi_set_grid_cells_per_record: the grid's cells per record (0: the product's choice) */
     /* fmgi_set_option: the tests' handles on product paths a given scene would not take (include/flatmatch_gi.h) */
-    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0};
+    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0, -1};
     bool compact = false;
     std::vector<RectC> h_rectc;
     std::vector<ClassC> h_classc;
@@ -1513,6 +1513,8 @@ FMGI_API int fmgi_experiments(void) { return FMGI_EXPERIMENTS; }
 
 FMGI_API int fmgi_set_option(fmgi_context *c, int option, int64_t value) {
     if (!c || option <= 0 || option >= FMGI_OPT_COUNT) return set_err(FMGI_ERR_ARG, "fmgi_set_option: bad option %d", option);
+    if (option == FMGI_OPT_PHOTON_LOCK && (value < -1 || value > 1))
+        return set_err(FMGI_ERR_ARG, "fmgi_set_option: photon_lock is -1 (auto), 0 or 1");
     c->opt[option] = value;
     return FMGI_OK;
 }
@@ -1672,6 +1674,23 @@ static int kernel_instance(const fmgi_context *c, int kernel) {
 /* the accumulations that store lane by lane (no rings: built for 6 waves per SIMD, every table staged) */
 static bool acc_by_lane(int accum) { return accum == kAccScatter || accum == kAccShared; }
 
+/* AUTO's choice of the wave-locked loop, per configuration class, measured in one process (profiles/wave_locked):
+   the staged closed box takes it (box200: k_bake + fold 66.18 -> 64.39 ms, the arms' min-max ranges 0.54 and
+   0.36 ms); the compact one gains nothing (box2000: 82.37 against 82.32 ms, ranges 2.2 ms) and keeps the
+   per-lane loop */
+constexpr bool kPhotonLockAutoStaged = true, kPhotonLockAutoCompact = false;
+/* whether a bake of instance `inst` with accumulation `accum` runs the wave-locked loop (FMGI_KVAR_LOCKED): only
+   the staged and compact closed boxes have one (the staged: FX3, STATE and the lane-by-lane stores; the compact:
+   the lane-by-lane stores) */
+static bool photon_lock_wanted(const fmgi_context *c, int inst, int accum) {
+    const bool staged = inst == (FMGI_KERNEL_GRID | FMGI_KVAR_AXES | FMGI_KVAR_STAGED);
+    const bool compact = inst == (FMGI_KERNEL_GRID | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT);
+    if (!(acc_by_lane(accum) ? (staged || compact) : (staged && (accum == FMGI_ACCUM_FX3 || accum == FMGI_ACCUM_STATE))))
+        return false;
+    if (c->opt[FMGI_OPT_PHOTON_LOCK] >= 0) return c->opt[FMGI_OPT_PHOTON_LOCK] == 1;
+    return acc_by_lane(accum) && (staged ? kPhotonLockAutoStaged : kPhotonLockAutoCompact);
+}
+
 static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool trace) {
     StagePlan p;
     const char *be = fmgi_exp_env("FMGI_BLOCK");
@@ -1718,6 +1737,13 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
        cannot */
     const int blocks_ring[] = {256, 512, 1024}, blocks_scatter[] = {256, 512, 768, 1024};
     const bool scat = acc_by_lane(accum);
+    /* a closed box the wave-locked loop was asked for with FX3 or STATE (photon_lock = 1: tests): its instance
+       reads every table from LDS, so the walls, the cells and their overflow records are staged wherever they
+       fit, as FMGI_CELLS_LDS=1 does, whatever the wave count */
+    const bool lock_all = c->opt[FMGI_OPT_PHOTON_LOCK] == 1 && kernel == FMGI_KERNEL_GRID && grid_axes_scene(c) &&
+                          c->cells_lds && (accum == FMGI_ACCUM_FX3 || accum == FMGI_ACCUM_STATE);
+    /* the cells' overflow records beside them: the lane-by-lane stores' plans */
+    const bool grecs = scat || lock_all;
     const int *blocks_all = scat ? blocks_scatter : blocks_ring;
     const int nblocks = scat ? 4 : 3;
     /* the grid cells in LDS: every cell lookup an LDS read instead of an L2 one. The closed boxes' coarse
@@ -1726,10 +1752,10 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
     const char *ce = fmgi_exp_env("FMGI_CELLS_LDS");
     /* (only the grid scan reads the staged GridCell copy: ScanHybrid's grid walk reads GridCellF from global
        memory, so staging for it would be dead LDS) */
-    const bool cells_forced = ce && atoi(ce) == 1 && kernel == FMGI_KERNEL_GRID;
+    const bool cells_forced = (ce && atoi(ce) == 1 && kernel == FMGI_KERNEL_GRID) || lock_all;
     bool cells = cells_forced || (!ce && c->cells_lds && kernel == FMGI_KERNEL_GRID);
     auto best = [&](bool rects, int &bb, int &bw) {
-        const int bytes = stage_bytes(c, kernel, rects, srcs, cells, scat, nullptr, nullptr);
+        const int bytes = stage_bytes(c, kernel, rects, srcs, cells, grecs, nullptr, nullptr);
         bb = p.block;
         bw = waves(p.block, bytes);
         if (forced_block) return;
@@ -1747,7 +1773,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
         /* the walls in LDS take the winners' records off the vector-memory path, which is what binds the
            bake (TA busy 98 %, profiles/r03/s3): worth a wave per SIMD (box200: 16 waves per CU with the
            walls staged 77.6 ms, 20 waves without 123.8 ms), not two */
-        rects = rects_mode == 1 ? w1 > 0 : (w1 > 0 && w1 >= std::min(w0, 16));
+        rects = (rects_mode == 1 || lock_all) ? w1 > 0 : (w1 > 0 && w1 >= std::min(w0, 16));
     }
     if (cells) { /* staged only if they fit (forced) or keep the wave count of the plan without them */
         const int wc = rects ? w1 : w0;
@@ -1763,7 +1789,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
         }
     }
     p.block = rects ? b1 : b0;
-    p.bytes = stage_bytes(c, kernel, rects, srcs, cells, scat, &p.rects_off, &p.srcs_off, &p.cells_off,
+    p.bytes = stage_bytes(c, kernel, rects, srcs, cells, grecs, &p.rects_off, &p.srcs_off, &p.cells_off,
                           &p.grecs_off,
                           &p.gidx_off);
     return p;
@@ -1927,6 +1953,11 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
         sp.grecs_off >= 0 && c->ngeneral == 0 && !fmgi_exp_env("FMGI_NO_STAGED"))
         inst |= FMGI_KVAR_STAGED;
     if (inst == (FMGI_KERNEL_GRID | FMGI_KVAR_AXES) && sp.rectc_off >= 0) inst |= FMGI_KVAR_COMPACT;
+    /* the staged and compact closed boxes' lanes run in step (a photon leaves a closed box only by accident): the
+       wave-locked loop (k_bake_locked) traces them with wave-uniform photon control. photon_lock = 0 / 1 forces
+       the per-lane / the locked loop (tests, A/B runs); AUTO by what measured faster in one process (profiles/
+       wave_locked) */
+    if (photon_lock_wanted(c, inst, kacc)) inst |= FMGI_KVAR_LOCKED;
     /* a closed box built with the coarse LDS grid (5 cells per record) but launched without the cells staged
        reads that coarser grid from L2, slower than the 16-per-record grid it replaced: said once per context */
     if (c->cells_lds && kernel == FMGI_KERNEL_GRID && sp.cells_off < 0 && sp.rectc_off < 0 && !c->warned_cells &&

@@ -307,6 +307,7 @@ constexpr int kAccShared = 10; /* the bucket layout stored lane by lane into per
 #define FMGI_KVAR_PLAN 0x200 /* FMGI_KERNEL_HYBRID | this: the walls over the floor plan (BakeArgs::plan_off) */
 #define FMGI_KVAR_STAGED 0x400 /* FMGI_KERNEL_GRID | FMGI_KVAR_AXES | this: walls, emitters and cells all in LDS */
 #define FMGI_KVAR_COMPACT 0x800 /* FMGI_KERNEL_GRID | FMGI_KVAR_AXES | this: the compact tables (RectC ...) in LDS */
+#define FMGI_KVAR_LOCKED 0x1000 /* ... | FMGI_KVAR_STAGED or _COMPACT | this: the wave-locked photon loop (k_bake_locked) */
 hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace, int grid_blocks, int block,
                             hipStream_t s);
 int fmgi_bake_resident_blocks(int kernel, int accum, bool trace, int block, int lds_bytes);

@@ -871,6 +871,8 @@ struct ScanGridT {
        in LDS): the global-memory paths of those tables are compiled out, so the bake loop issues no global
        load but its rare fallbacks' and work-item fetches' */
     static constexpr bool kStaged = Staged;
+    /* the closed boxes' lanes run in step (no photon leaves but by accident): k_bake_locked can trace them */
+    static constexpr bool kLockable = Axes && Staged;
     static constexpr int kMinWaves = 4; /* k_bake occupancy floor for the register allocator */
     static constexpr int kOrderedRounds = 12;
 
@@ -2625,6 +2627,218 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake(BakeArgs a) {
 #endif
 }
 
+/* ---- the wave-locked photon loop (closed boxes) ------------------------------------------------ */
+
+/* whether a scan has a wave-locked instance (ScanGridT::kLockable: the staged and compact closed boxes) */
+template <class Scan, class = void>
+struct ScanLockable {
+    static constexpr bool value = false;
+};
+template <class Scan>
+struct ScanLockable<Scan, decltype((void)Scan::kLockable)> {
+    static constexpr bool value = Scan::kLockable;
+};
+
+__device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+/*
+ * k_bake for scenes no photon leaves but by accident (closed boxes: ~6.5e-6 escapes per photon). Every work
+ * item is FMGI_PHOTONS_PER_ITEM photons and a photon that does not escape takes exactly FMGI_MAX_DEPTH scans,
+ * so the lanes of a wave that fetch their items together stay in step for the whole item. This loop says so:
+ * a wave takes 64 consecutive fetch indices with one atomic, and the photon counter, the depth, "first scan"
+ * and "last bounce" are wave-uniform values and scalar branches instead of per-lane state. A lane whose photon
+ * escapes is parked (`alive`) until the wave starts its next photon; its RNG state is what k_bake's lane has
+ * after an escape, so the item's draws are the same. Lanes past the end of the launch (`has`) sit a round out.
+ * The lightmap and every counter are integer sums over items: which lane traces an item, and when, changes
+ * no bit. Every loop is bounded by the item counter, the photons of an item and the depth.
+ * Scans and escapes are counted per wave from the lane masks (s_bcnt1), not per lane.
+ */
+template <class Scan, class Acc, bool TRACE>
+__global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a) {
+    static_assert(ScanLockable<Scan>::value && Scan::kLds && !Scan::kCoop && ScanTail<Scan>::value == 0,
+                  "the wave-locked loop is built for the staged closed-box scans");
+    extern __shared__ __attribute__((aligned(16))) char s_img[];
+    uint32_t *const ring = acc_region<Acc>(s_img, a);
+    {
+        const int n16 = a.fimg_bytes >> 4;
+        for (int i = threadIdx.x; i < n16; i += blockDim.x) ((uint4 *)s_img)[i] = ((const uint4 *)a.fimg)[i];
+        __syncthreads();
+    }
+    if constexpr (HasAppend<Acc>::value)
+        Acc::init(a, ring);
+    uint32_t rng = 0;
+    f3 pos = mkf3(0, 0, 0), dir = mkf3(0, 0, 0), col = mkf3(0, 0, 0);
+    f3 sn = mkf3(0, 0, 0), sbu = mkf3(0, 0, 0), sbv = mkf3(0, 0, 0); /* pending diffuse sample basis */
+    int sid = 0, srci = 0;
+    bool win = false;
+    uint64_t item = 0; /* (TRACE) */
+    int nev = 0;       /* (TRACE) */
+    unsigned long long w_ph = 0, w_scan = 0; /* the wave's counts of one launch (wave-uniform) */
+    uint32_t w_esc = 0;
+    ScanStats sst;
+    WaveStream ws;
+    sst.clk.reset();
+    const uint64_t nitems = a.item_end - a.item_begin;
+    for (;;) { /* one round: an item for each lane of the wave */
+        uint64_t w = 0;
+        if (__lane_id() == 0) w = atomicAdd(a.counter, 64ull);
+        w = first_lane64(w);
+        if (w >= nitems) break;
+        w += __lane_id();
+        const bool has = w < nitems;
+        w_ph += (uint32_t)(FMGI_PHOTONS_PER_ITEM * __popcll(__ballot(has)));
+        if (has) {
+            if (uni(a.fetch_nseg) > 0) { /* fetch order, as k_bake */
+                const uint32_t f = (uint32_t)w;
+                int lo = 0, hi = a.fetch_nseg - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (a.fetch_tab[2 * mid] <= f) lo = mid; else hi = mid - 1;
+                }
+                w = a.fetch_tab[2 * lo + 1] + (f - a.fetch_tab[2 * lo]);
+            } else {
+                w += a.item_begin;
+            }
+            item = w;
+            int li;
+            uint32_t gid;
+            locate_item(a, w, srci, li, gid);
+            /* the item's scans, per source: FMGI_MAX_DEPTH a photon, less what an escape cuts short (below) */
+            if (uni(a.src_cost))
+                atomicAdd(a.src_cost + srci, (unsigned long long)(FMGI_PHOTONS_PER_ITEM * FMGI_MAX_DEPTH));
+            rng = gid + (uint32_t)a.launches[li].rng_offset; /* photonmap.cl:272 */
+            const float r40 = rng_next(rng) * 40; /* photonmap.cl:273-275 */
+            const int k = (int)ceilf(r40);
+            rng = c_jump.a[k] * rng + c_jump.c[k];
+            win = srci < a.nwindows;
+            nev = 0;
+        }
+#pragma nounroll
+        for (int left = FMGI_PHOTONS_PER_ITEM; left; left--) {
+            bool alive = has, pend = false;
+#pragma nounroll
+            for (int depth = 0; depth < FMGI_MAX_DEPTH; depth++) {
+                bool dep = false, esc = false;
+                uint32_t code = 0;
+                w_scan += (uint32_t)__popcll(__ballot(alive));
+                if (alive) {
+                    /* ---- stage 1: the photon's emission, then the iteration's one direction sample ---- */
+                    float edx = 0, edy = 0;
+                    if (depth == 0) {
+                        const SrcDev S = load_src<true>(a, s_img, srci);
+                        col = win ? mkf3(18, 18, 18) : mkf3(16, 16, 18); /* photonmap.cl:167-169 */
+                        sid = win ? (512 + 1) : 1;
+                        edx = rng_next(rng);
+                        edy = rng_next(rng);
+                        sn = mkf3(S.nx, S.ny, S.nz);
+                        sbu = mkf3(S.bux, S.buy, S.buz);
+                        sbv = mkf3(S.bvx, S.bvy, S.bvz);
+                    }
+                    sst.clk.lap(ST_START);
+                    if (depth == 0 || pend) dir = sample_dir(rng, sn, sbu, sbv, depth == 0 && win);
+                    if (depth == 0) {
+                        const SrcDev S = load_src<true>(a, s_img, srci);
+                        pos = add3(add3(add3(mkf3(S.px, S.py, S.pz), mul3(mkf3(S.wx, S.wy, S.wz), edx)),
+                                        mul3(mkf3(S.hx, S.hy, S.hz), edy)),
+                                   mul3(dir, 1e-5f));
+                    } else {
+                        pos = add3(pos, mul3(dir, 1e-5f)); /* photonmap.cl:261 */
+                    }
+                    pend = false;
+                    sst.clk.lap(ST_SAMPLE);
+
+                    /* ---- stage 2: scan ---- */
+                    HitRec h;
+                    Scan::scan(a, s_img, pos, dir, h, sst);
+                    sst.clk.lap(ST_SCAN1);
+                    sn = mkf3(h.nx, h.ny, h.nz);
+                    sbu = mkf3(h.bux, h.buy, h.buz);
+                    sbv = mkf3(h.bvx, h.bvy, h.bvz);
+                    if (h.best == INFINITY) { /* photonmap.cl:208-209: parked until the wave's next photon */
+                        alive = false;
+                        esc = true;
+                        if (uni(a.src_cost))
+                            atomicAdd(a.src_cost + srci, 0ull - (unsigned long long)(FMGI_MAX_DEPTH - 1 - depth));
+                    } else {
+                        /* ---- stage 3: hit (photonmap.cl:216-258) ---- */
+                        pos = add3(pos, mul3(dir, h.best));
+                        const f3 hn = mkf3(h.nx, h.ny, h.nz);
+                        const int texel = h.base + tile_uv(h.dx, h.dy, h.wl, h.hl, h.iwl, h.ihl, h.W, h.H);
+                        const bool last = depth + 1 == FMGI_MAX_DEPTH;
+                        if (pos.z > 4.99999965541064739227294921875e-4f || rng_next(rng) > 0.75f) {
+                            const bool floor = pos.z < 1e-5f;
+                            if (floor) {
+                                col.y *= 0.85f;
+                                col.z *= 0.7f;
+                            }
+                            col = mul3(col, 0.9f);
+                            sid = (sid & 512) | ((sid & 511) << 1) | (floor ? 1 : 0);
+                            if (last) {
+                                rng = lcg2(rng); /* the direction of a photon that ends here is never used */
+                            } else {
+                                pend = true; /* sampled at the top of the next iteration */
+                            }
+                        } else {
+                            const float two = 2.0f * dot3(hn, dir);
+                            dir = sub3(dir, mul3(hn, two));
+                        }
+                        Acc::deposit(a, texel, sid, col);
+                        dep = true;
+                        code = ((uint32_t)texel << 10) | (uint32_t)sid;
+                        if (TRACE) {
+                            EventDev e;
+                            e.photon = FMGI_PHOTONS_PER_ITEM - left;
+                            e.depth = depth;
+                            e.rect = h.idx;
+                            e.texel = texel;
+                            e.rgb[0] = col.x;
+                            e.rgb[1] = col.y;
+                            e.rgb[2] = col.z;
+                            e.rng = pend ? lcg2(rng) : rng; /* RNG state after this bounce's sample */
+                            ((EventDev *)a.events)[(item - a.item_begin) * FMGI_EVENTS_PER_ITEM + nev] = e;
+                            nev++;
+                        }
+                    }
+                    sst.clk.lap(ST_HIT);
+                }
+                w_esc += (uint32_t)__popcll(__ballot(esc));
+                if constexpr (HasAppend<Acc>::value) Acc::append(a, ws, ring, dep, code);
+                sst.clk.lap(ST_APPEND);
+            }
+        }
+        if (has) { /* once per item, as k_bake */
+            if (TRACE) {
+                a.ev_counts[item - a.item_begin] = nev;
+                a.rng_final[item - a.item_begin] = rng;
+            }
+            if (sst.tests) atomicAdd(a.stats + KSTAT_TESTS, (unsigned long long)sst.tests);
+        }
+        sst.tests = 0;
+    }
+    if constexpr (HasAppend<Acc>::value) Acc::finish(a, ws, ring);
+
+    if ((threadIdx.x & 63) == 0) {
+        if (w_ph) atomicAdd(a.stats + KSTAT_PHOTONS, w_ph);
+        if (w_scan) atomicAdd(a.stats + KSTAT_SCANS, w_scan);
+        if (w_scan - w_esc) atomicAdd(a.stats + KSTAT_DEPOSITS, w_scan - w_esc);
+        if (w_esc) atomicAdd(a.stats + KSTAT_ESCAPES, (unsigned long long)w_esc);
+    }
+    const unsigned long long v[3] = {(unsigned long long)sst.ties + sst.invalid, sst.ties, sst.invalid};
+    const int slot[3] = {KSTAT_RESCANS, KSTAT_TIES, KSTAT_INVALID};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        unsigned long long s = wave_sum(v[i]);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(a.stats + slot[i], s);
+    }
+#ifdef FMGI_STAGE_TIMING
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < ST_N; k++) atomicAdd(a.stats + KSTAT_STAGE0 + k, sst.clk.acc[k]);
+#endif
+}
+
 /* AccState -> int64 fixed point: lm[t][c] += sum_s counts[s][t] * colour_fx[s][c]; counts zeroed.
    One thread per texel; each read of counts[s][*] is coalesced across the block. */
 __global__ __launch_bounds__(256) void k_reduce_states(unsigned long long *__restrict__ counts,
@@ -2792,6 +3006,41 @@ const void *kernel_ptr(bool trace) {
     return trace ? (const void *)&k_bake<Scan, Acc, true> : (const void *)&k_bake<Scan, Acc, false>;
 }
 
+/* the wave-locked instances (FMGI_KVAR_LOCKED): the accumulations a closed box is baked with (FX3, STATE and the
+   lane-by-lane stores of the bucket layout) */
+template <class Scan, class Acc>
+const void *locked_ptr(bool trace) {
+    return trace ? (const void *)&k_bake_locked<Scan, Acc, true> : (const void *)&k_bake_locked<Scan, Acc, false>;
+}
+template <class Scan>
+const void *locked_acc(int accum, bool trace) {
+    if (accum == kAccShared) return locked_ptr<Scan, AccShared>(trace);
+    if (accum == kAccScatter) return locked_ptr<Scan, AccScatter>(trace);
+    if constexpr (ScanWaves<Scan>::value == 0) { /* (the compact instance: the lane-by-lane stores only) */
+        if (accum == 1) return locked_ptr<Scan, AccFx3>(trace);
+        if (accum == 2) return locked_ptr<Scan, AccState>(trace);
+    }
+    return nullptr;
+}
+template <class Scan, class Acc>
+void launch_locked3(const BakeArgs &a, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (trace)
+        hipLaunchKernelGGL((k_bake_locked<Scan, Acc, true>), grid, block, lds, s, a);
+    else
+        hipLaunchKernelGGL((k_bake_locked<Scan, Acc, false>), grid, block, lds, s, a);
+}
+template <class Scan>
+bool launch_locked(const BakeArgs &a, int accum, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (!locked_acc<Scan>(accum, trace)) return false;
+    if (accum == kAccShared) launch_locked3<Scan, AccShared>(a, trace, grid, block, lds, s);
+    else if (accum == kAccScatter) launch_locked3<Scan, AccScatter>(a, trace, grid, block, lds, s);
+    else if constexpr (ScanWaves<Scan>::value == 0) {
+        if (accum == 2) launch_locked3<Scan, AccState>(a, trace, grid, block, lds, s);
+        else launch_locked3<Scan, AccFx3>(a, trace, grid, block, lds, s);
+    }
+    return true;
+}
+
 /* accumulation codes: FMGI_ACCUM_FX3 1, STATE 2, NONE 3, STREAM 4 (unsorted / presorted layouts) and the
    internal kAccBucket 5 (STREAM in the per-tile bucket layout) */
 /* (the experiment build's accumulations: the presorted-segment stream, per-workgroup tile lines, the dense
@@ -2834,6 +3083,12 @@ bool launch_acc(const BakeArgs &a, int accum, bool trace, dim3 grid, dim3 block,
 }
 
 const void *bake_kernel(int kernel, int accum, bool trace) {
+    if (kernel & FMGI_KVAR_LOCKED) { /* the wave-locked loop of the staged and compact closed boxes */
+        kernel &= ~FMGI_KVAR_LOCKED;
+        if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) return locked_acc<ScanGridAxesCompact>(accum, trace);
+        if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) return locked_acc<ScanGridAxesStaged>(accum, trace);
+        return nullptr;
+    }
     if (kernel == FMGI_KERNEL_FAST_COOP)
         return accum == kAccBucket ? kernel_ptr<ScanFastCoop, AccBucket>(false)
                : accum == kAccScatter ? kernel_ptr<ScanFastCoop, AccScatter>(false)
@@ -2942,7 +3197,12 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
         if (e != hipSuccess) return e;
     }
     bool ok = true;
-    if (kernel == FMGI_KERNEL_FAST_COOP) {
+    if (kernel & FMGI_KVAR_LOCKED) {
+        const int k = kernel & ~FMGI_KVAR_LOCKED;
+        if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) ok = launch_locked<ScanGridAxesCompact>(a, accum, trace, grid, blk, lds, s);
+        else if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) ok = launch_locked<ScanGridAxesStaged>(a, accum, trace, grid, blk, lds, s);
+        else ok = false;
+    } else if (kernel == FMGI_KERNEL_FAST_COOP) {
         if (trace || !bake_kernel(kernel, accum, false)) return hipErrorInvalidValue;
         if (accum == kAccBucket) launch3<ScanFastCoop, AccBucket>(a, false, grid, blk, lds, s);
         else if (accum == kAccScatter) launch3<ScanFastCoop, AccScatter>(a, false, grid, blk, lds, s);

@@ -336,7 +336,7 @@ class Context:
 
     def set_option(self, name: str, value: int):
         """fmgi_set_option: one of _lib.OPTIONS (chunk_items, pool_limit, stream_layout, bucket_fill, wide_tiles,
-        coop, no_axes); takes effect at the next bake (no_axes: the next set_scene)."""
+        coop, no_axes, photon_lock); takes effect at the next bake (no_axes: the next set_scene)."""
         from ._lib import OPTIONS
 
         check(self.lib.fmgi_set_option(self.h, OPTIONS[name], int(value)), "fmgi_set_option")

@@ -98,7 +98,7 @@ FILTER_MAX_RADIUS = 16
 FILTER_MAX_MAPS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
-           "no_axes": 7}
+           "no_axes": 7, "photon_lock": 8}
 
 
 class FmgiError(RuntimeError):

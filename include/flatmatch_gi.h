@@ -433,7 +433,9 @@ int fmgi_experiments(void);
                             per-workgroup tile blocks; -1: by the tables' LDS fit
      FMGI_OPT_WIDE_TILES    0 / 1: 2048- / 4096-texel bucket tiles; -1: by the launch size
      FMGI_OPT_COOP          2, 4, 8: lanes per work item of ScanFast's small launches; 0: by the launch size
-     FMGI_OPT_NO_AXES       1: closed boxes through the general grid instance (its sorted <= 4-slot phase 1) */
+     FMGI_OPT_NO_AXES       1: closed boxes through the general grid instance (its sorted <= 4-slot phase 1)
+     FMGI_OPT_PHOTON_LOCK   0 / 1: the staged and compact closed boxes through the per-lane / the wave-locked
+                            photon loop; -1: by the configuration (any other value: FMGI_ERR_ARG) */
 #define FMGI_OPT_CHUNK_ITEMS 1
 #define FMGI_OPT_POOL_LIMIT 2
 #define FMGI_OPT_STREAM_LAYOUT 3
@@ -441,7 +443,8 @@ int fmgi_experiments(void);
 #define FMGI_OPT_WIDE_TILES 5
 #define FMGI_OPT_COOP 6
 #define FMGI_OPT_NO_AXES 7
-#define FMGI_OPT_COUNT 8
+#define FMGI_OPT_PHOTON_LOCK 8
+#define FMGI_OPT_COUNT 9
 int fmgi_set_option(fmgi_context *ctx, int option, int64_t value);
 /* Profiling builds only (make timing -> libflatmatch_gi_timing.so, -DFMGI_STAGE_TIMING): shader-clock
    cycles summed over waves per bake-loop stage {start, sample, scan phase 1, phase 2, fallback, hit,
