@@ -314,6 +314,161 @@ static uint32_t grid_bounds(float c, float hw, float o, float inv, int cell) {
     return grid_q(a, o, inv, cell) | (grid_q(b, o, inv, cell) << 16);
 }
 
+/*
+ * The lattice descriptors of a closed box (LatticeDesc, ScanGridT's Lattice instances): each of the six
+ * (axis, class) lists must hold one plane whose records form a uniform nu x nv lattice with rect index
+ * base + i su + j sv. Nothing is taken from the geometry on trust: a candidate lattice and band are accepted only
+ * after the kernel's cell arithmetic, replayed here in float32, has been checked against the filter's own float
+ * test on every float. Per axis and column i the floats the kernel calls sure (cell i, lo <= fraction <= hi) form
+ * an interval, since every op is monotone in the coordinate; its ends are found by bisection over the ordered
+ * float keys. That interval must lie inside the passing interval [grid_end(lo), grid_end(hi)] of every record of
+ * column i and be disjoint from that of every record of another column. The record test is the product of its
+ * two axis tests, so a point sure on both axes passes exactly one record, the one of cell (i, j), whose index is
+ * checked against base + i su + j sv. The band starts at twice the neighbours' overlap plus the rounding of the
+ * cell coordinate and is doubled, a few times and up to 1/8, until it verifies; a plane that never does leaves
+ * the scene without a lattice (all or nothing).
+ */
+struct LatticeAxis {
+    float o = 0, inv = 0, m = 0, lo = 0, hi = 0;
+    int n = 0;
+};
+/* the kernel's lattice arithmetic on one coordinate: the cell and the fraction inside it */
+static void lattice_cell(float x, const LatticeAxis &A, float &cell, float &frac) {
+    const float d = x - A.o;
+    const float r = d * A.inv;
+    const float t = std::min(std::max(r, 0.0f), A.m); /* med3(r, 0, m) for m >= 0 and r not NaN */
+    cell = floorf(t);
+    frac = r - cell;
+}
+/* one axis: centres[k], half-widths[k] and column col[k] of the plane's records; C[i] the column centres */
+static bool lattice_axis(const std::vector<float> &rc, const std::vector<float> &rhw, const std::vector<int> &col,
+                         const std::vector<double> &C, double scale, LatticeAxis &A) {
+    const int n = (int)C.size();
+    const size_t R = rc.size();
+    std::vector<double> hwmax((size_t)n, 0.0), hwmin((size_t)n, 1e300);
+    for (size_t k = 0; k < R; k++) {
+        if (!(rhw[k] >= 0) || !grid_pass(rc[k], rc[k], rhw[k])) return false;
+        hwmax[(size_t)col[k]] = std::max(hwmax[(size_t)col[k]], (double)rhw[k]);
+        hwmin[(size_t)col[k]] = std::min(hwmin[(size_t)col[k]], (double)rhw[k]);
+    }
+    double P = n > 1 ? (C[(size_t)n - 1] - C[0]) / (n - 1) : 2.0 * hwmin[0];
+    if (!(P > 0)) return false;
+    double ov = 0; /* widest overlap of two neighbouring columns' passing extents */
+    for (int i = 0; i + 1 < n; i++)
+        ov = std::max(ov, (C[(size_t)i] + hwmax[(size_t)i]) - (C[(size_t)i + 1] - hwmax[(size_t)i + 1]));
+    if (n == 1) ov = 0;
+    A.o = (float)(C[0] - 0.5 * P);
+    A.inv = (float)(1.0 / P);
+    A.n = n;
+    A.m = (float)(n - 1);
+    /* the records' passing intervals, once */
+    std::vector<float> pa(R), pb(R);
+    for (size_t k = 0; k < R; k++) {
+        pa[k] = grid_end(rc[k], rhw[k], false);
+        pb[k] = grid_end(rc[k], rhw[k], true);
+    }
+    /* per side of a shared edge the overlap itself (the two sides together: twice the overlap), plus a few ulps
+       of the cell coordinate and of the hit point in cell units */
+    double band = std::max(ov, 0.0) / P + 4.0 * 0x1p-23 * ((double)n + scale / P);
+    for (int attempt = 0; attempt < 6 && band <= 0.125; attempt++, band *= 2.0) {
+        A.lo = (float)band;
+        A.hi = (float)(1.0 - band);
+        bool ok = true;
+        for (int i = 0; i < n && ok; i++) {
+            const float fi = (float)i;
+            /* monotone in x: at or past the sure interval's start / at or before its end */
+            auto t_lo = [&](float x) { float c, f; lattice_cell(x, A, c, f); return c > fi || (c == fi && f >= A.lo); };
+            auto t_hi = [&](float x) { float c, f; lattice_cell(x, A, c, f); return c < fi || (c == fi && f <= A.hi); };
+            const float mid = (float)C[(size_t)i];
+            if (!t_lo(mid) || !t_hi(mid) || t_lo(-INFINITY) || t_hi(INFINITY)) { ok = false; break; }
+            int64_t in = float_key(mid), out = float_key(-INFINITY);
+            while (in - out > 1) {
+                const int64_t h = out + (in - out) / 2;
+                if (t_lo(key_float(h))) in = h; else out = h;
+            }
+            const float sa = key_float(in);
+            in = float_key(mid), out = float_key(INFINITY);
+            while (out - in > 1) {
+                const int64_t h = in + (out - in) / 2;
+                if (t_hi(key_float(h))) in = h; else out = h;
+            }
+            const float sb = key_float(in);
+            for (size_t k = 0; k < R && ok; k++) {
+                if (col[k] == i) ok = pa[k] <= sa && sb <= pb[k];
+                else ok = pb[k] < sa || pa[k] > sb;
+            }
+        }
+        if (ok) return true;
+    }
+    return false;
+}
+static bool build_lattice(const FilterBuild &fb, std::vector<LatticeDesc> &out) {
+    out.clear();
+    if (!fb.general.empty()) return false;
+    for (int a = 0; a < 3; a++)
+        for (int c = 0; c < 2; c++) {
+            const std::vector<FilterRec> &L = fb.cls[a][c];
+            if (L.empty() || L.size() >= (size_t)1 << 22) return false;
+            double hmin = 1e300;
+            for (const FilterRec &r : L) {
+                if (memcmp(&r.plane, &L[0].plane, 4) != 0) return false; /* one plane per class */
+                hmin = std::min(hmin, (double)std::min(r.hwu, r.hwv));
+            }
+            if (!(hmin > 0)) return false;
+            /* columns and rows: the records' centres, those closer than a quarter of the narrowest half-width merged */
+            auto columns = [&](bool is_u, std::vector<double> &C, std::vector<int> &col) {
+                std::vector<double> v;
+                for (const FilterRec &r : L) v.push_back(is_u ? r.cu : r.cv);
+                std::sort(v.begin(), v.end());
+                std::vector<double> lo_, hi_;
+                for (double x : v) {
+                    if (lo_.empty() || x - hi_.back() > 0.25 * hmin) lo_.push_back(x), hi_.push_back(x);
+                    else hi_.back() = x;
+                }
+                C.clear();
+                for (size_t i = 0; i < lo_.size(); i++) C.push_back(0.5 * (lo_[i] + hi_[i]));
+                col.clear();
+                for (const FilterRec &r : L) {
+                    const double x = is_u ? r.cu : r.cv;
+                    size_t i = 0;
+                    while (i + 1 < lo_.size() && x > hi_[i]) i++;
+                    col.push_back((int)i);
+                }
+            };
+            std::vector<double> CU, CV;
+            std::vector<int> colu, colv;
+            columns(true, CU, colu);
+            columns(false, CV, colv);
+            const size_t nu = CU.size(), nv = CV.size();
+            if (nu * nv != L.size() || nu >= 4096 || nv >= 4096) return false;
+            std::vector<int32_t> id(nu * nv, -1);
+            for (size_t k = 0; k < L.size(); k++) {
+                int32_t &slot = id[(size_t)colv[k] * nu + (size_t)colu[k]];
+                if (slot >= 0 || L[k].idx < 0) return false; /* one record per lattice cell */
+                slot = L[k].idx;
+            }
+            LatticeDesc d;
+            memset(&d, 0, sizeof d);
+            d.base = id[0];
+            d.su = nu > 1 ? id[1] - id[0] : 0;
+            d.sv = nv > 1 ? id[nu] - id[0] : 0;
+            for (size_t j = 0; j < nv; j++)
+                for (size_t i = 0; i < nu; i++)
+                    if (id[j * nu + i] != d.base + (int32_t)i * d.su + (int32_t)j * d.sv) return false;
+            std::vector<float> rc, rhw;
+            LatticeAxis AU, AV;
+            for (const FilterRec &r : L) rc.push_back(r.cu), rhw.push_back(r.hwu);
+            if (!lattice_axis(rc, rhw, colu, CU, fb.scale, AU)) return false;
+            rc.clear(), rhw.clear();
+            for (const FilterRec &r : L) rc.push_back(r.cv), rhw.push_back(r.hwv);
+            if (!lattice_axis(rc, rhw, colv, CV, fb.scale, AV)) return false;
+            d.u0 = AU.o, d.iu = AU.inv, d.mu = AU.m, d.lo_u = AU.lo, d.hi_u = AU.hi, d.nu = AU.n;
+            d.v0 = AV.o, d.iv = AV.inv, d.mv = AV.m, d.lo_v = AV.lo, d.hi_v = AV.hi, d.nv = AV.n;
+            out.push_back(d);
+        }
+    return true;
+}
+
 /* cells per record the grid's cost model may spend when forced (FMGI_GRID_CPR, experiment builds; 0 if unset);
    fmgi_set_grid_cells_per_record sets it per context (tests of the grids the product builds) */
 static int grid_cpr_env() {
@@ -774,7 +929,10 @@ struct fmgi_context {
     std::string last_kernel; /* fmgi_last_bake_kernel: the instance(s) the last bake launch ran */
     int grid_cpr = 0; /* fmgi_set_grid_cells_per_record: the grid's cells per record (0: the product's choice) */
     /* fmgi_set_option: the tests' handles on product paths a given scene would not take (include/flatmatch_gi.h) */
-    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0, -1};
+    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0, -1, -1};
+    /* the closed box's six verified lattice descriptors (build_lattice; fmgi_lattice_copy), in the plane image's
+       order and uploaded after it in d_gimg; empty: the scene has no lattice */
+    std::vector<LatticeDesc> h_lattice;
     bool compact = false;
     std::vector<RectC> h_rectc;
     std::vector<ClassC> h_classc;
@@ -1177,9 +1335,30 @@ static bool hybrid_full(const fmgi_context *c) {
     return !fmgi_kernels_filter_pk() || (c->plan_off >= 0 && pe && atoi(pe) == 1) || (fe && atoi(fe) == 1);
 }
 
+/* AUTO's choice of the lattice instances, per configuration class, by the wave-locked loop's rule and measured in
+   one process (profiles/lattice): the median k_bake + fold must be lower than the other arm's by more than the sum
+   of the two arms' min-max ranges. The staged closed box takes it (box200: 64.29 -> 56.58 ms, ranges 0.22 and 0.62
+   ms), and so does the compact one (box2000: 82.44 -> 77.63 ms, ranges 1.84 and 1.81 ms) */
+#ifndef FMGI_LATTICE_AUTO_STAGED /* (make fullvariant VFLAGS=-DFMGI_LATTICE_AUTO_STAGED=0/1: bench.py A/B of the choice) */
+#define FMGI_LATTICE_AUTO_STAGED 1
+#endif
+#ifndef FMGI_LATTICE_AUTO_COMPACT
+#define FMGI_LATTICE_AUTO_COMPACT 1
+#endif
+constexpr bool kLatticeAutoStaged = FMGI_LATTICE_AUTO_STAGED != 0, kLatticeAutoCompact = FMGI_LATTICE_AUTO_COMPACT != 0;
+/* whether a grid bake of this scene stages the lattice descriptors after the plane image and, where its instance
+   is a staged or compact closed box, runs the lattice instance (FMGI_KVAR_LATTICE): lattice = 1 / 0 forces it on
+   (for a scene with a verified lattice) / off; AUTO by the measurement */
+static bool lattice_on(const fmgi_context *c) {
+    if (c->h_lattice.empty() || c->opt[FMGI_OPT_LATTICE] == 0) return false;
+    if (c->opt[FMGI_OPT_LATTICE] == 1) return true;
+    return c->compact ? kLatticeAutoCompact : kLatticeAutoStaged;
+}
+
 static int image_bytes(const fmgi_context *c, int kernel) {
     if (kernel == FMGI_KERNEL_HYBRID) return hybrid_full(c) ? c->himg_full_bytes : c->himg_bytes;
-    return kernel == FMGI_KERNEL_GRID ? c->gimg_bytes : c->fimg_bytes;
+    if (kernel == FMGI_KERNEL_GRID) return c->gimg_bytes + (lattice_on(c) ? kLatticeBytes : 0);
+    return c->fimg_bytes;
 }
 
 static bool kernel_fits(const fmgi_context *c, int kernel, int accum, int block) {
@@ -1368,6 +1547,11 @@ FMGI_API int fmgi_set_scene(fmgi_context *c, const fmgi_rect *walls, int num_wal
     c->compact = false;
     for (int a = 0; a < 3; a++) c->gJ[a] = gb.J[a];
     c->gimg_bytes = (int)(gb.img.size() * sizeof(GridPlane));
+    /* closed boxes: the six planes as verified lattices, or none (the descriptors' LDS offset is the box's image) */
+    c->h_lattice.clear();
+    if (gb.J[0] == 1 && gb.J[1] == 1 && gb.J[2] == 1 && !no_axes(c) && c->gimg_bytes == kLatticeBytes &&
+        !build_lattice(fb, c->h_lattice))
+        c->h_lattice.clear();
     c->grid_cells = (int)gb.cells.size();
     c->grid_entries = (int)gb.idx.size();
     c->h_grid = gb;
@@ -1458,7 +1642,14 @@ FMGI_API int fmgi_set_scene(fmgi_context *c, const fmgi_rect *walls, int num_wal
     c->d_gcellsF = nullptr;
     c->d_grecs = nullptr;
     c->d_gidx = nullptr;
-    HIPCHK(upload(&c->d_gimg, gb.img));
+    {   /* the plane image, then the lattice descriptors (staged with it when a bake runs a lattice instance) */
+        std::vector<GridPlane> img = gb.img;
+        static_assert(sizeof(LatticeDesc) == sizeof(GridPlane), "the descriptors extend the plane image");
+        img.resize(gb.img.size() + c->h_lattice.size());
+        if (!c->h_lattice.empty())
+            memcpy(img.data() + gb.img.size(), c->h_lattice.data(), c->h_lattice.size() * sizeof(LatticeDesc));
+        HIPCHK(upload(&c->d_gimg, img));
+    }
     HIPCHK(upload(&c->d_gcells, gb.cells));
     HIPCHK(upload(&c->d_gcellsF, gb.cellsF));
     {   /* ScanHybrid's full image: the filter image (a multiple of 64 B), the plane image, the plan, the pairs */
@@ -1515,6 +1706,8 @@ FMGI_API int fmgi_set_option(fmgi_context *c, int option, int64_t value) {
     if (!c || option <= 0 || option >= FMGI_OPT_COUNT) return set_err(FMGI_ERR_ARG, "fmgi_set_option: bad option %d", option);
     if (option == FMGI_OPT_PHOTON_LOCK && (value < -1 || value > 1))
         return set_err(FMGI_ERR_ARG, "fmgi_set_option: photon_lock is -1 (auto), 0 or 1");
+    if (option == FMGI_OPT_LATTICE && (value < -1 || value > 1))
+        return set_err(FMGI_ERR_ARG, "fmgi_set_option: lattice is -1 (auto), 0 or 1");
     c->opt[option] = value;
     return FMGI_OK;
 }
@@ -1632,6 +1825,7 @@ struct StagePlan {
     int bytes = 0;                   /* staged blob = image (16-B aligned) | rects | srcs | cells | overflow */
     int rects_off = -1, srcs_off = -1, cells_off = -1, grecs_off = -1, gidx_off = -1;
     int rectc_off = -1, class_off = -1, recf_off = -1, cellc_off = -1; /* the compact closed-box tables */
+    bool lattice = false;            /* the image is the plane image and the lattice descriptors (lattice_on) */
 };
 
 static int stage_bytes(const fmgi_context *c, int kernel, bool rects, bool srcs, bool cells, bool grecs, int *roff,
@@ -1700,23 +1894,28 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
     if (c->compact && kernel == FMGI_KERNEL_GRID && acc_by_lane(accum) && c->nsrcs > 0 && !forced_block) {
         /* the compact closed box: image | emitters | classes | RectC | filter extents | cells, one 1024-lane
            workgroup per CU (the tables take most of its LDS) */
-        int off = (c->gimg_bytes + 15) & ~15;
-        p.srcs_off = off;
-        off += c->nsrcs * (int)sizeof(SrcDev);
-        p.class_off = off;
-        off += (int)(c->h_classc.size() * sizeof(ClassC));
-        p.rectc_off = off;
-        off += (int)((c->h_rectc.size() * sizeof(RectC) + 15) & ~(size_t)15);
-        p.recf_off = off;
-        off += (int)(c->h_recf.size() * sizeof(float));
-        p.cellc_off = off;
-        off += (int)(c->h_cellc.size() * sizeof(uint32_t));
-        p.bytes = (off + 15) & ~15;
-        p.block = 1024;
-        const int inst = FMGI_KERNEL_GRID | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT;
-        if (fmgi_bake_lds(inst, accum, p.block, p.bytes, nullptr) <= kBakeLdsMax &&
-            fmgi_bake_resident_blocks(inst, accum, trace, p.block, p.bytes) >= 1)
-            return p;
+        /* (with the lattice descriptors if they still fit beside the tables, else without them) */
+        for (int lat = lattice_on(c) ? 1 : 0; lat >= 0; lat--) {
+            p = StagePlan{};
+            p.lattice = lat != 0;
+            int off = (c->gimg_bytes + (lat ? kLatticeBytes : 0) + 15) & ~15;
+            p.srcs_off = off;
+            off += c->nsrcs * (int)sizeof(SrcDev);
+            p.class_off = off;
+            off += (int)(c->h_classc.size() * sizeof(ClassC));
+            p.rectc_off = off;
+            off += (int)((c->h_rectc.size() * sizeof(RectC) + 15) & ~(size_t)15);
+            p.recf_off = off;
+            off += (int)(c->h_recf.size() * sizeof(float));
+            p.cellc_off = off;
+            off += (int)(c->h_cellc.size() * sizeof(uint32_t));
+            p.bytes = (off + 15) & ~15;
+            p.block = 1024;
+            const int inst = FMGI_KERNEL_GRID | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT;
+            if (fmgi_bake_lds(inst, accum, p.block, p.bytes, nullptr) <= kBakeLdsMax &&
+                fmgi_bake_resident_blocks(inst, accum, trace, p.block, p.bytes) >= 1)
+                return p;
+        }
         p = StagePlan{}; /* (does not launch: the general planning below) */
     }
     const char *se = fmgi_exp_env("FMGI_SRCS_LDS"), *re = fmgi_exp_env("FMGI_RECTS_LDS");
@@ -1788,6 +1987,7 @@ static StagePlan plan_stage(const fmgi_context *c, int kernel, int accum, bool t
             b0 = nb0, w0 = nw0, b1 = nb1, w1 = nw1;
         }
     }
+    p.lattice = kernel == FMGI_KERNEL_GRID && lattice_on(c); /* (image_bytes counts the descriptors) */
     p.block = rects ? b1 : b0;
     p.bytes = stage_bytes(c, kernel, rects, srcs, cells, grecs, &p.rects_off, &p.srcs_off, &p.cells_off,
                           &p.grecs_off,
@@ -1958,6 +2158,12 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
        the per-lane / the locked loop (tests, A/B runs); AUTO by what measured faster in one process (profiles/
        wave_locked) */
     if (photon_lock_wanted(c, inst, kacc)) inst |= FMGI_KVAR_LOCKED;
+    /* a closed box with a verified lattice (build_lattice) whose plan staged the descriptors: the nearest plane's
+       lattice cell instead of its grid cell (FMGI_KVAR_LATTICE; the instances exist for the wave-locked loop and
+       for the per-lane loop's lane-by-lane stores). lattice = 1 on a scene without a lattice runs the ordinary
+       instance. */
+    if (sp.lattice && (inst & (FMGI_KVAR_STAGED | FMGI_KVAR_COMPACT)) && ((inst & FMGI_KVAR_LOCKED) || acc_by_lane(kacc)))
+        inst |= FMGI_KVAR_LATTICE;
     /* a closed box built with the coarse LDS grid (5 cells per record) but launched without the cells staged
        reads that coarser grid from L2, slower than the 16-per-record grid it replaced: said once per context */
     if (c->cells_lds && kernel == FMGI_KERNEL_GRID && sp.cells_off < 0 && sp.rectc_off < 0 && !c->warned_cells &&
@@ -1989,7 +2195,7 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
     a.stats = c->d_stats;
     if (kernel == FMGI_KERNEL_GRID) {
         a.fimg = c->d_gimg;
-        a.fimg_bytes = c->gimg_bytes;
+        a.fimg_bytes = c->gimg_bytes + (sp.lattice ? kLatticeBytes : 0); /* (d_gimg: the planes, then the descriptors) */
         for (int k = 0; k < 3; k++) a.fJ[k] = c->gJ[k];
         a.gcells = c->d_gcells;
         a.gcellsF = c->d_gcellsF;
@@ -2024,7 +2230,7 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
     a.rectc_off = a.class_off = a.recf_off = a.cellc_off = -1;
     a.cdummy = c->nrects;
     if (sp.rectc_off >= 0) { /* the compact blob: image | srcs | classes | RectC | filter extents | cells */
-        const uint64_t key = (c->scene_gen << 9) | 0x1FFu;
+        const uint64_t key = (c->scene_gen << 10) | 0x1FFu | (sp.lattice ? 0x200u : 0u);
         if (c->blob_key != key) {
             if (c->blob_cap < (size_t)sp.bytes) {
                 HIPCHK(hipStreamSynchronize(s)); /* no earlier bake may still stage the old blob */
@@ -2057,7 +2263,7 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
         a.recf_off = sp.recf_off;
         a.cellc_off = sp.cellc_off;
     } else if (sp.rects_off >= 0 || sp.srcs_off >= 0 || sp.cells_off >= 0) { /* the blob: image | rects | srcs | cells */
-        const uint64_t key = (c->scene_gen << 9) | (sp.grecs_off >= 0 ? 0x100u : 0u) |
+        const uint64_t key = (c->scene_gen << 10) | (sp.lattice ? 0x200u : 0u) | (sp.grecs_off >= 0 ? 0x100u : 0u) |
                              (kernel == FMGI_KERNEL_HYBRID && hybrid_full(c) ? 0x40u : 0u) |
                              ((uint64_t)(kernel & 0xF) << 2) | (sp.rects_off >= 0 ? 2u : 0u) | (sp.srcs_off >= 0 ? 1u : 0u) |
                              (sp.cells_off >= 0 ? 0x80u : 0u);
@@ -2823,6 +3029,12 @@ FMGI_API int fmgi_grid_copy(const fmgi_context *c, void *planes, void *cells, fl
     if (recs) memcpy(recs, g.recs.data(), g.recs.size() * sizeof(float));
     if (idx) memcpy(idx, g.idx.data(), g.idx.size() * sizeof(int32_t));
     return FMGI_OK;
+}
+
+FMGI_API int fmgi_lattice_copy(const fmgi_context *c, void *desc) {
+    if (!c) return set_err(FMGI_ERR_ARG, "fmgi_lattice_copy: null context");
+    if (desc && !c->h_lattice.empty()) memcpy(desc, c->h_lattice.data(), c->h_lattice.size() * sizeof(LatticeDesc));
+    return (int)c->h_lattice.size();
 }
 
 FMGI_API int fmgi_get_stats(fmgi_context *c, fmgi_stats *out) {

@@ -77,6 +77,22 @@ struct GridCell {
 };
 static_assert(sizeof(GridCell) == 32, "GridCell must be 32 B");
 constexpr uint32_t kGridNoRec = 0xFFFFu; /* lo 0xFFFF, hi 0: no q passes */
+
+/* One plane of a closed box whose records form a uniform nu x nv lattice of rects (fmgi_api.cpp build_lattice,
+   FMGI_KVAR_LATTICE): the kernel maps a hit point to its lattice cell (i, j) and the cell fractions (fu, fv) with
+   ru = (uh - u0) * iu, cu = floor(med3(ru, 0, mu)), fu = ru - cu (likewise v). Inside the band lo <= f <= hi on
+   both axes exactly one record of the plane passes the float filter test, and it is rect base + i * su + j * sv
+   (the host verifies this with the filter's own float ops before it accepts the lattice). The six descriptors
+   follow the plane image in its order: per axis {+a class, -a class}. */
+struct LatticeDesc {
+    float u0, iu, mu, lo_u;
+    float v0, iv, mv, lo_v;
+    float hi_u, hi_v;
+    int32_t base, su;
+    int32_t sv, nu, nv, pad;
+};
+static_assert(sizeof(LatticeDesc) == 64, "LatticeDesc must be 64 B");
+constexpr int kLatticeBytes = 6 * (int)sizeof(LatticeDesc); /* after the closed box's 6 x 64-B plane image */
 /* the same cell with float records (centre, half-extent; absent: half-extent -1), read by the general
    grid walks (many planes per scan), where the 16-bit cell coordinates cost more per visited plane than
    the 16 B they save */
@@ -308,6 +324,7 @@ constexpr int kAccShared = 10; /* the bucket layout stored lane by lane into per
 #define FMGI_KVAR_STAGED 0x400 /* FMGI_KERNEL_GRID | FMGI_KVAR_AXES | this: walls, emitters and cells all in LDS */
 #define FMGI_KVAR_COMPACT 0x800 /* FMGI_KERNEL_GRID | FMGI_KVAR_AXES | this: the compact tables (RectC ...) in LDS */
 #define FMGI_KVAR_LOCKED 0x1000 /* ... | FMGI_KVAR_STAGED or _COMPACT | this: the wave-locked photon loop (k_bake_locked) */
+#define FMGI_KVAR_LATTICE 0x2000 /* ... | FMGI_KVAR_STAGED or _COMPACT | this: the nearest plane's lattice cell (LatticeDesc) */
 hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace, int grid_blocks, int block,
                             hipStream_t s);
 int fmgi_bake_resident_blocks(int kernel, int accum, bool trace, int block, int lds_bytes);

@@ -783,7 +783,38 @@ __device__ __forceinline__ void grid_axes_visit(const BakeArgs &a, const char *i
     grid_cell_tests<Staged>(a, img, load_cell<Staged>(a, img, ci), f, uh, vh, qu, qv, L1, L2, code1, ntest);
 }
 
-template <bool Staged, bool Compact = false>
+/* the nearest plane's grid cell and its candidate tests (staged or global cells, or the compact tables) */
+template <bool Staged, bool Compact>
+__device__ __forceinline__ void grid_nearest_cell(const BakeArgs &a, const char *img, const float4 *p, float fm, float uh,
+                                                  float vh, float &L1, float &L2, int &code1, unsigned &ntest) {
+    if (Compact) {
+        grid_cell_tests_c(a, img, grid_cell_idx(p[0], p[1], p[2], uh, vh), fm, uh, vh, L1, L2, code1, ntest);
+    } else {
+        uint32_t qu, qv;
+        const uint32_t ci = grid_cell(p[0], p[1], p[2], uh, vh, qu, qv);
+        grid_cell_tests<Staged>(a, img, load_cell<Staged>(a, img, ci), fm, uh, vh, qu, qv, L1, L2, code1, ntest);
+    }
+}
+
+/*
+ * Lattice = true (closed boxes whose six planes the host verified as uniform lattices of rects, LatticeDesc
+ * after the plane image): on the nearest plane the hit point's lattice cell (i, j) and cell fractions (fu, fv)
+ * come from the descriptor alone. Inside the band on both axes the scan takes L1 = fm, code1 = base + i su +
+ * j sv and leaves L2 as it is, with no cell, record or overflow read; every other point (the band along the
+ * rects' edges, clamped points, NaN) runs the cell path unchanged.
+ * Why that is exact: the host accepts a lattice only after it has found, with the float filter's own ops
+ * (grid_pass, grid_end), that for every float the kernel's arithmetic calls sure in column i, the u test
+ * |fl(uh - c)| <= hw passes for the records of column i and fails for those of every other column, and likewise
+ * for rows; the record test is the product of the two, so a point sure on both axes passes exactly the record
+ * of rect idx(i, j). (L1, L2, code1) are then what the float filter's phase 1 (grid_rec over the plane's
+ * records) yields for this plane: one key fm below L1 = INFINITY, every other key INFINITY, L2 unchanged. The
+ * comment above ScanFast proves that filter's candidate set a superset of the valid set, so phase 2, the
+ * separation test and the fallbacks carry over. The cells' quantized inline bounds are a superset of the float
+ * filter's: the cell path can see a second candidate (a tie, resolved by ordered_exact to the same hit) where
+ * the lattice sees one, so `ties` and `invalid` may fall and `tests` does; hits, deposits and RNG draws do not
+ * change.
+ */
+template <bool Staged, bool Compact = false, bool Lattice = false>
 __device__ __forceinline__ void grid_phase1_axes(const BakeArgs &a, const char *img, f3 s, f3 d, float &L1,
                                                  float &L2, int &code1, unsigned &ntest) {
     const float fx0 = (*(const float *)(img + (d.x < 0.0f ? 0 : 64)) - s.x) * __builtin_amdgcn_rcpf(d.x);
@@ -804,12 +835,26 @@ __device__ __forceinline__ void grid_phase1_axes(const BakeArgs &a, const char *
         const float du = (m == 0) ? d.y : d.x, dv = mz ? d.y : d.z;
         const float4 *p = (const float4 *)__builtin_assume_aligned(img + 128 * m + (dm < 0.0f ? 0 : 64), 16);
         const float uh = fmaf(du, fm, su), vh = fmaf(dv, fm, sv);
-        if (Compact) {
-            grid_cell_tests_c(a, img, grid_cell_idx(p[0], p[1], p[2], uh, vh), fm, uh, vh, L1, L2, code1, ntest);
+        if (Lattice) {
+            /* the plane's LatticeDesc, kLatticeBytes (= the closed box's plane image) after its GridPlane:
+               q0 = {u0, iu, mu, lo_u}, q1 = {v0, iv, mv, lo_v}, q2 = {hi_u, hi_v, base, su}, then sv */
+            const float4 *q = p + kLatticeBytes / 16;
+            const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+            const int lsv = *(const int *)(q + 3);
+            const float ru = (uh - q0.x) * q0.y, rv = (vh - q1.x) * q1.y;
+            const float cu = __builtin_floorf(__builtin_amdgcn_fmed3f(ru, 0.0f, q0.z));
+            const float cv = __builtin_floorf(__builtin_amdgcn_fmed3f(rv, 0.0f, q1.z));
+            const float fu = ru - cu, fv = rv - cv;
+            const bool sure = (int)(fu >= q0.w) & (int)(fu <= q2.x) & (int)(fv >= q1.w) & (int)(fv <= q2.y);
+            if (sure) {
+                L1 = fm;
+                code1 = __mul24((int)cv, lsv) + (__mul24((int)cu, __float_as_int(q2.w)) + __float_as_int(q2.z));
+                ntest += 1;
+            } else {
+                grid_nearest_cell<Staged, Compact>(a, img, p, fm, uh, vh, L1, L2, code1, ntest);
+            }
         } else {
-            uint32_t qu, qv;
-            const uint32_t ci = grid_cell(p[0], p[1], p[2], uh, vh, qu, qv);
-            grid_cell_tests<Staged>(a, img, load_cell<Staged>(a, img, ci), fm, uh, vh, qu, qv, L1, L2, code1, ntest);
+            grid_nearest_cell<Staged, Compact>(a, img, p, fm, uh, vh, L1, L2, code1, ntest);
         }
     }
     const int m = mz ? 2 : (my ? 1 : 0); /* the others, within the band above the current L1 (1 + 2^-11) */
@@ -859,14 +904,16 @@ __device__ __forceinline__ void grid_visit(const BakeArgs &a, const char *lds, i
 /* Axes = true: the closed-box specialisation (one plane per axis and class, BakeArgs::grid_axes), whose
    kernel holds grid_phase1_axes alone: the general kernel's register and SGPR budget is set by its layout
    walks, and its spilled SGPRs come back as v_readlane in the box scan too */
-template <bool Axes, bool Staged = false, bool Compact = false>
-struct ScanGridT {
+template <bool Axes, bool Staged, bool Compact, bool Lattice>
+struct ScanGridImpl {
     static_assert(!Compact || (Axes && Staged), "the compact tables exist for the staged closed-box instance");
+    static_assert(!Lattice || (Axes && Staged), "the lattice descriptors are staged after the closed box's plane image");
     static constexpr bool kLds = true;
     static constexpr bool kCoop = false;
     /* Compact: one 1024-lane workgroup per CU holds the ~150 KB of compact tables, i.e. 4 waves per SIMD, so the
        instance takes the registers of 4 */
     static constexpr int kWaves = Compact ? 4 : 0;
+    static constexpr bool kCompactTables = Compact;
     /* Staged (closed boxes whose walls, emitters, grid cells and the cells' overflow records the plan stages
        in LDS): the global-memory paths of those tables are compiled out, so the bake loop issues no global
        load but its rare fallbacks' and work-item fetches' */
@@ -921,7 +968,7 @@ struct ScanGridT {
         int code1 = -1;
         unsigned ntest = 0;
         if (Axes) {
-            grid_phase1_axes<Staged, Compact>(a, lds, src, dir, L1, L2, code1, ntest);
+            grid_phase1_axes<Staged, Compact, Lattice>(a, lds, src, dir, L1, L2, code1, ntest);
         } else if (a.fJ[0] + a.fJ[1] + a.fJ[2] <= 4) {
             grid_phase1_sorted(a, lds, src, dir, L1, L2, code1, ntest);
         } else {
@@ -976,10 +1023,22 @@ struct ScanGridT {
     }
 };
 
+/* the instances' types (their names are what a profiler prints): ScanGridT for the grid-cell scans, and
+   ScanGridLatticeT<ScanGridT<true, true, Compact>> for the staged and compact closed boxes that take the nearest
+   plane's lattice cell (FMGI_KVAR_LATTICE, grid_phase1_axes) and are otherwise that instance */
+template <bool Axes, bool Staged = false, bool Compact = false>
+struct ScanGridT : ScanGridImpl<Axes, Staged, Compact, false> {};
+template <class Base>
+struct ScanGridLatticeT : ScanGridImpl<true, true, Base::kCompactTables, true> {
+    static_assert(Base::kLockable, "the lattice instances are the staged and compact closed boxes'");
+};
+
 using ScanGrid = ScanGridT<false>;
 using ScanGridAxes = ScanGridT<true>;
 using ScanGridAxesStaged = ScanGridT<true, true>;
 using ScanGridAxesCompact = ScanGridT<true, true, true>;
+using ScanGridAxesStagedLat = ScanGridLatticeT<ScanGridAxesStaged>;
+using ScanGridAxesCompactLat = ScanGridLatticeT<ScanGridAxesCompact>;
 
 /*
  * ScanHybrid's wall pass over the floor plan (Plan = true; tables: fmgi_api.cpp build_plan, which holds
@@ -3087,8 +3146,20 @@ const void *bake_kernel(int kernel, int accum, bool trace) {
         kernel &= ~FMGI_KVAR_LOCKED;
         if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) return locked_acc<ScanGridAxesCompact>(accum, trace);
         if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) return locked_acc<ScanGridAxesStaged>(accum, trace);
+        if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT | FMGI_KVAR_LATTICE))
+            return locked_acc<ScanGridAxesCompactLat>(accum, trace);
+        if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED | FMGI_KVAR_LATTICE))
+            return locked_acc<ScanGridAxesStagedLat>(accum, trace);
         return nullptr;
     }
+    /* the lattice instances of the per-lane loop: the lane-by-lane stores only (the accumulations a staged or
+       compact closed box runs that loop with, bake_common) */
+    if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT | FMGI_KVAR_LATTICE))
+        return accum == kAccScatter ? kernel_ptr<ScanGridAxesCompactLat, AccScatter>(trace)
+               : accum == kAccShared ? kernel_ptr<ScanGridAxesCompactLat, AccShared>(trace) : nullptr;
+    if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED | FMGI_KVAR_LATTICE))
+        return accum == kAccScatter ? kernel_ptr<ScanGridAxesStagedLat, AccScatter>(trace)
+               : accum == kAccShared ? kernel_ptr<ScanGridAxesStagedLat, AccShared>(trace) : nullptr;
     if (kernel == FMGI_KERNEL_FAST_COOP)
         return accum == kAccBucket ? kernel_ptr<ScanFastCoop, AccBucket>(false)
                : accum == kAccScatter ? kernel_ptr<ScanFastCoop, AccScatter>(false)
@@ -3201,6 +3272,10 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
         const int k = kernel & ~FMGI_KVAR_LOCKED;
         if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT)) ok = launch_locked<ScanGridAxesCompact>(a, accum, trace, grid, blk, lds, s);
         else if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) ok = launch_locked<ScanGridAxesStaged>(a, accum, trace, grid, blk, lds, s);
+        else if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT | FMGI_KVAR_LATTICE))
+            ok = launch_locked<ScanGridAxesCompactLat>(a, accum, trace, grid, blk, lds, s);
+        else if (k == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED | FMGI_KVAR_LATTICE))
+            ok = launch_locked<ScanGridAxesStagedLat>(a, accum, trace, grid, blk, lds, s);
         else ok = false;
     } else if (kernel == FMGI_KERNEL_FAST_COOP) {
         if (trace || !bake_kernel(kernel, accum, false)) return hipErrorInvalidValue;
@@ -3231,6 +3306,14 @@ hipError_t fmgi_launch_bake(const BakeArgs &a, int kernel, int accum, bool trace
         if (accum == kAccShared) launch3<ScanGridAxesCompact, AccShared>(a, trace, grid, blk, lds, s);
         else if (accum != kAccScatter) return hipErrorInvalidValue;
         else launch3<ScanGridAxesCompact, AccScatter>(a, trace, grid, blk, lds, s);
+    } else if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_COMPACT | FMGI_KVAR_LATTICE)) { /* ... with the lattice */
+        if (accum == kAccShared) launch3<ScanGridAxesCompactLat, AccShared>(a, trace, grid, blk, lds, s);
+        else if (accum != kAccScatter) return hipErrorInvalidValue;
+        else launch3<ScanGridAxesCompactLat, AccScatter>(a, trace, grid, blk, lds, s);
+    } else if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED | FMGI_KVAR_LATTICE)) {
+        if (accum == kAccShared) launch3<ScanGridAxesStagedLat, AccShared>(a, trace, grid, blk, lds, s);
+        else if (accum != kAccScatter) return hipErrorInvalidValue;
+        else launch3<ScanGridAxesStagedLat, AccScatter>(a, trace, grid, blk, lds, s);
     } else if (kernel == (2 | FMGI_KVAR_AXES | FMGI_KVAR_STAGED)) { /* closed box, every table in LDS */
         ok = launch_acc<ScanGridAxesStaged>(a, accum, trace, grid, blk, lds, s);
     } else if (kernel == (2 | FMGI_KVAR_AXES)) { /* FMGI_KERNEL_GRID, closed box */

@@ -336,7 +336,7 @@ class Context:
 
     def set_option(self, name: str, value: int):
         """fmgi_set_option: one of _lib.OPTIONS (chunk_items, pool_limit, stream_layout, bucket_fill, wide_tiles,
-        coop, no_axes, photon_lock); takes effect at the next bake (no_axes: the next set_scene)."""
+        coop, no_axes, photon_lock, lattice); takes effect at the next bake (no_axes: the next set_scene)."""
         from ._lib import OPTIONS
 
         check(self.lib.fmgi_set_option(self.h, OPTIONS[name], int(value)), "fmgi_set_option")
@@ -357,6 +357,15 @@ class Context:
         check(self.lib.fmgi_grid_copy(self.h, _ptr(planes), _ptr(cells), _ptr(recs), _ptr(idx)), "fmgi_grid_copy")
         return {"J": [int(x) for x in sz[:3]], "planes": planes[: 2 * npairs], "cells": cells, "recs": recs,
                 "idx": idx}
+
+    def lattice_tables(self) -> dict:
+        """The closed box's lattice descriptors (include/flatmatch_gi.h fmgi_lattice_copy): {"lattice": [6]
+        records of LATTICE_DTYPE, per axis {+n plane, -n plane}}, empty when the scene has no verified lattice."""
+        n = check(self.lib.fmgi_lattice_copy(self.h, None), "fmgi_lattice_copy")
+        desc = np.zeros(n, LATTICE_DTYPE)
+        if n:
+            check(self.lib.fmgi_lattice_copy(self.h, _ptr(desc)), "fmgi_lattice_copy")
+        return {"lattice": desc}
 
     def plan_tables(self) -> dict | None:
         """FMGI_KERNEL_HYBRID's floor plan of the walls (include/flatmatch_gi.h fmgi_plan_copy), or None."""
@@ -426,6 +435,11 @@ assert GRID_PLANE_DTYPE.itemsize == 64
 GRID_CELL_DTYPE = np.dtype([("q0", "<u4", (2,)), ("q1", "<u4", (2,)), ("count", "<i4"), ("idx0", "<i4"),
                             ("idx1", "<i4"), ("rest", "<i4")])
 assert GRID_CELL_DTYPE.itemsize == 32
+LATTICE_DTYPE = np.dtype([("u0", "<f4"), ("iu", "<f4"), ("mu", "<f4"), ("lo_u", "<f4"),
+                          ("v0", "<f4"), ("iv", "<f4"), ("mv", "<f4"), ("lo_v", "<f4"),
+                          ("hi_u", "<f4"), ("hi_v", "<f4"), ("base", "<i4"), ("su", "<i4"),
+                          ("sv", "<i4"), ("nu", "<i4"), ("nv", "<i4"), ("pad", "<i4")])
+assert LATTICE_DTYPE.itemsize == 64
 
 
 def make_geometry(sc: Scene, texels: np.ndarray):

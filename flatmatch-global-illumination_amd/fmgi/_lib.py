@@ -46,6 +46,7 @@ EXPORTS = (
     "fmgi_experiments",
     "fmgi_set_option",
     "fmgi_grid_copy",
+    "fmgi_lattice_copy",
     "fmgi_plan_copy",
     "fmgi_filter_copy",
     "fmgi_pairs_copy",
@@ -98,7 +99,7 @@ FILTER_MAX_RADIUS = 16
 FILTER_MAX_MAPS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
-           "no_axes": 7, "photon_lock": 8}
+           "no_axes": 7, "photon_lock": 8, "lattice": 9}
 
 
 class FmgiError(RuntimeError):
@@ -305,6 +306,7 @@ def load() -> C.CDLL:
         "fmgi_filter_radii": (C.c_int, [vp, vp, u64, C.c_int, vp, vp]),
         "fmgi_filter_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
+        "fmgi_lattice_copy": (C.c_int, [vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),
         "fmgi_filter_copy": (C.c_int, [vp, vp, vp, vp]),
         "fmgi_pairs_copy": (C.c_int, [vp, vp, vp, vp]),

@@ -435,7 +435,11 @@ int fmgi_experiments(void);
      FMGI_OPT_COOP          2, 4, 8: lanes per work item of ScanFast's small launches; 0: by the launch size
      FMGI_OPT_NO_AXES       1: closed boxes through the general grid instance (its sorted <= 4-slot phase 1)
      FMGI_OPT_PHOTON_LOCK   0 / 1: the staged and compact closed boxes through the per-lane / the wave-locked
-                            photon loop; -1: by the configuration (any other value: FMGI_ERR_ARG) */
+                            photon loop; -1: by the configuration (any other value: FMGI_ERR_ARG)
+     FMGI_OPT_LATTICE       0 / 1: the staged and compact closed boxes whose six planes are verified lattices of
+                            rects (fmgi_lattice_copy) through their grid cells / the lattice cell of the nearest
+                            plane; -1: by the configuration (any other value: FMGI_ERR_ARG). A scene without a
+                            lattice runs its ordinary instance whatever the value. */
 #define FMGI_OPT_CHUNK_ITEMS 1
 #define FMGI_OPT_POOL_LIMIT 2
 #define FMGI_OPT_STREAM_LAYOUT 3
@@ -444,13 +448,22 @@ int fmgi_experiments(void);
 #define FMGI_OPT_COOP 6
 #define FMGI_OPT_NO_AXES 7
 #define FMGI_OPT_PHOTON_LOCK 8
-#define FMGI_OPT_COUNT 9
+#define FMGI_OPT_LATTICE 9
+#define FMGI_OPT_COUNT 10
 int fmgi_set_option(fmgi_context *ctx, int option, int64_t value);
 /* Profiling builds only (make timing -> libflatmatch_gi_timing.so, -DFMGI_STAGE_TIMING): shader-clock
    cycles summed over waves per bake-loop stage {start, sample, scan phase 1, phase 2, fallback, hit,
    append}, since the last fmgi_reset_stats; all zero in the normal library. */
 int fmgi_get_stage_cycles(fmgi_context *ctx, uint64_t out[16]);
 int fmgi_grid_copy(const fmgi_context *ctx, void *planes, void *cells, float *recs, int32_t *idx);
+/* The lattice descriptors of a closed box (built and verified by fmgi_set_scene; host-only contexts too): returns
+   6 when every plane of the box is a uniform lattice of rects, else 0, and with desc != NULL copies them, per
+   axis {plane of the +n class, plane of the -n class}, each {float u0, iu, mu, lo_u, v0, iv, mv, lo_v, hi_u, hi_v;
+   int32 base, su, sv, nu, nv, pad} (64 B). A hit point (uh, vh) of the plane lies in lattice cell
+   cu = floor(clamp((uh - u0) * iu, 0, mu)) at fraction fu = (uh - u0) * iu - cu (likewise v), all in float32;
+   where lo_u <= fu <= hi_u and lo_v <= fv <= hi_v, exactly one record of the plane passes the filter test and it
+   is rect base + cu * su + cv * sv. */
+int fmgi_lattice_copy(const fmgi_context *ctx, void *desc);
 /* FMGI_KERNEL_HYBRID's floor plan of the walls (built by fmgi_set_scene; host-only contexts too; the
    hybrid scan walks it with FMGI_PLAN=1): *bytes = its size (0: no plan for this scene); with
    blob != NULL and *bytes >= that size, copies it: {float x0, y0, 1 / cs, cs}, {int32 nx | ny << 16,
