@@ -34,6 +34,7 @@
 #include "fmgi_internal.h"
 #include "fmgi_filter.h"
 #include "fmgi_recolour.h"
+#include "fmgi_sparse.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
 
@@ -877,6 +878,8 @@ struct fmgi_context {
     std::vector<uint32_t> h_recolour_tab;
     hipEvent_t ev_recolour = nullptr;
     bool recolour_pending = false;
+    /* fmgi_sparse_measure: the four sums its count kernel adds up (a SparseSums), read back before it returns */
+    SparseSums *d_sparse_sums = nullptr;
     /* fmgi_filter_radii / fmgi_filter_apply: the walls' lightmapSetup {s0, s1, s2} (kept by
        fmgi_set_scene), the texel / wall / column tables built from them on the first filter call of a scene, and
        the prefix-sum scratch (u64 [planes][num_texels], grown on demand); a later call's stream waits for
@@ -1027,6 +1030,7 @@ FMGI_API void fmgi_destroy(fmgi_context *c) {
     hipFree(c->d_colfx);
     if (c->ev_recolour) { hipEventSynchronize(c->ev_recolour); hipEventDestroy(c->ev_recolour); }
     hipFree(c->d_recolour_tab);
+    hipFree(c->d_sparse_sums);
     if (c->ev_filter) { hipEventSynchronize(c->ev_filter); hipEventDestroy(c->ev_filter); }
     hipFree(c->d_filter_tex);
     hipFree(c->d_filter_walls);
@@ -2752,27 +2756,16 @@ FMGI_API int fmgi_bake_states(fmgi_context *c, uint64_t item_begin, uint64_t ite
     return rc;
 }
 
-FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
-                           int num_scenarios, void *const *lm_fx_dev, void *stream) {
-    if (!c || !counts_dev || !palettes || !lm_fx_dev || num_groups < 1 || num_scenarios < 1)
-        return set_err(FMGI_ERR_ARG, "fmgi_recolour: bad arguments");
-    const int G = num_groups, K = num_scenarios;
-    for (int g = 0; g < G; g++)
-        if (!counts_dev[g]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: histogram %d is NULL", g);
-    for (int k = 0; k < K; k++)
-        if (!lm_fx_dev[k]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: lightmap %d is NULL", k);
-    for (int64_t i = 0; i < (int64_t)K * G; i++)
-        if (!palette_ok(&palettes[i]))
-            return set_err(FMGI_ERR_ARG, "fmgi_recolour: palette of scenario %lld, group %lld outside 0 <= window, light "
-                                         "< 32, 0 <= floor_tint, albedo <= 1", (long long)(i / G), (long long)(i % G));
-    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_recolour: no scene");
-    /* one launch per pass (<= 8 scenarios) and group; its table: u32 [1024][k][3] */
-    struct Launch {
-        int k0, kn, g;
-        size_t off;
-    };
-    std::vector<Launch> launches;
-    std::vector<uint32_t> tab;
+/* one launch per pass (<= 8 scenarios) and group; its table: u32 [1024][k][3] at tab[off] */
+struct RecolourLaunch {
+    int k0, kn, g;
+    size_t off;
+};
+
+/* the tables of K scenarios x G groups (palettes all palette_ok) and the launches that read them: a group
+   switched off in every scenario of a pass has no launch and no table */
+static void recolour_tables(const fmgi_palette *palettes, int G, int K, std::vector<RecolourLaunch> &launches,
+                            std::vector<uint32_t> &tab) {
     std::vector<int64_t> t64((size_t)FMGI_COLOUR_STATES * 3);
     for (int k0 = 0; k0 < K; k0 += kRecolourMaxK) {
         const int kn = std::min(kRecolourMaxK, K - k0);
@@ -2795,10 +2788,11 @@ FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int n
                 tab.resize(off); /* switched off in every scenario of the pass: not read */
         }
     }
-    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot recolour");
-    if (launches.empty()) return FMGI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+}
+
+/* the tables onto the device, on stream s: the table buffer is reused once the previous call's launches, which
+   still read it, have passed ev_recolour. The caller records ev_recolour after its last launch. */
+static int recolour_upload(fmgi_context *c, std::vector<uint32_t> &tab, hipStream_t s) {
     if (!c->ev_recolour) HIPCHK(hipEventCreateWithFlags(&c->ev_recolour, hipEventDisableTiming));
     if (c->recolour_pending) { /* the previous call's launches still read the tables */
         HIPCHK(hipEventSynchronize(c->ev_recolour));
@@ -2815,9 +2809,35 @@ FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int n
     HIPCHK(hipMemcpyAsync(c->d_recolour_tab, c->h_recolour_tab.data(), c->h_recolour_tab.size() * sizeof(uint32_t),
                           hipMemcpyHostToDevice, s));
     c->recolour_pending = true; /* (set before the launches: an error below must not free tables in use) */
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
+                           int num_scenarios, void *const *lm_fx_dev, void *stream) {
+    if (!c || !counts_dev || !palettes || !lm_fx_dev || num_groups < 1 || num_scenarios < 1)
+        return set_err(FMGI_ERR_ARG, "fmgi_recolour: bad arguments");
+    const int G = num_groups, K = num_scenarios;
+    for (int g = 0; g < G; g++)
+        if (!counts_dev[g]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: histogram %d is NULL", g);
+    for (int k = 0; k < K; k++)
+        if (!lm_fx_dev[k]) return set_err(FMGI_ERR_ARG, "fmgi_recolour: lightmap %d is NULL", k);
+    for (int64_t i = 0; i < (int64_t)K * G; i++)
+        if (!palette_ok(&palettes[i]))
+            return set_err(FMGI_ERR_ARG, "fmgi_recolour: palette of scenario %lld, group %lld outside 0 <= window, light "
+                                         "< 32, 0 <= floor_tint, albedo <= 1", (long long)(i / G), (long long)(i % G));
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_recolour: no scene");
+    std::vector<RecolourLaunch> launches;
+    std::vector<uint32_t> tab;
+    recolour_tables(palettes, G, K, launches, tab);
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot recolour");
+    if (launches.empty()) return FMGI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int up = recolour_upload(c, tab, s);
+    if (up != FMGI_OK) return up;
     const int slabs = fmgi_recolour_slabs(c->num_texels, c->num_cus);
     hipError_t err = hipSuccess;
-    for (const Launch &L : launches) {
+    for (const RecolourLaunch &L : launches) {
         RecolourArgs a;
         memset(&a, 0, sizeof a);
         a.counts = (const unsigned long long *)counts_dev[L.g];
@@ -2832,6 +2852,207 @@ FMGI_API int fmgi_recolour(fmgi_context *c, const void *const *counts_dev, int n
     const hipError_t ev = hipEventRecord(c->ev_recolour, s);
     if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_recolour: %s", hipGetErrorString(err));
     HIPCHK(ev);
+    return FMGI_OK;
+}
+
+/* ---- sparse photon histograms ---- */
+
+FMGI_API size_t fmgi_sparse_bytes(int num_texels, uint64_t rows) {
+    static_assert(FMGI_SPARSE_COUNT_BITS == kSparseCountBits && FMGI_SPARSE_COUNT_BITS + 10 == 64 &&
+                      FMGI_COLOUR_STATE_COUNT == 1 << 10, "an entry is a 10-bit state over a 54-bit count");
+    if (num_texels < 1) return 0;
+    return 8 * ((size_t)fmgi_sparse_blocks(num_texels) + 1) + 512 * (size_t)rows;
+}
+
+static const char *sparse_info_fault(const fmgi_sparse_info *info) {
+    if (!info) return "info is NULL";
+    if (info->num_texels < 1 || info->num_blocks != fmgi_sparse_blocks(info->num_texels))
+        return "info.num_blocks is not (info.num_texels + 63) / 64";
+    if (info->too_large != 0) return "info.too_large is not 0 (a count of 2^54 or more has no sparse form)";
+    return nullptr;
+}
+
+FMGI_API int fmgi_sparse_measure(fmgi_context *c, const void *counts_dev, fmgi_sparse_info *info, void *stream) {
+    if (!c || !counts_dev || !info) return set_err(FMGI_ERR_ARG, "fmgi_sparse_measure: bad arguments");
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_sparse_measure: no scene");
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot measure a histogram");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!c->d_sparse_sums) HIPCHK(hipMalloc(&c->d_sparse_sums, sizeof(SparseSums)));
+    HIPCHK(hipMemsetAsync(c->d_sparse_sums, 0, sizeof(SparseSums), s));
+    HIPCHK(fmgi_launch_sparse_count((const unsigned long long *)counts_dev, c->num_texels, nullptr, c->d_sparse_sums, s));
+    SparseSums sums;
+    HIPCHK(hipMemcpyAsync(&sums, c->d_sparse_sums, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    info->num_texels = c->num_texels;
+    info->num_blocks = fmgi_sparse_blocks(c->num_texels);
+    info->rows = sums.rows;
+    info->cells = sums.cells;
+    info->deposits = sums.deposits;
+    info->too_large = sums.too_large;
+    if (sums.too_large)
+        return set_err(FMGI_ERR_ARG, "fmgi_sparse_measure: %llu cells hold a count of 2^%d or more", sums.too_large,
+                       FMGI_SPARSE_COUNT_BITS);
+    return FMGI_OK;
+}
+
+/* the checks fmgi_sparse_compact and fmgi_sparse_expand share, in the documented order */
+static int sparse_call_check(const fmgi_context *c, const void *a, const void *b, const fmgi_sparse_info *info,
+                             const char *what) {
+    if (!c || !a || !b || !info) return set_err(FMGI_ERR_ARG, "%s: bad arguments", what);
+    if (const char *f = sparse_info_fault(info)) return set_err(FMGI_ERR_ARG, "%s: %s", what, f);
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "%s: no scene", what);
+    if (info->num_texels != c->num_texels)
+        return set_err(FMGI_ERR_ARG, "%s: info is of %d texels, the scene has %d", what, info->num_texels, c->num_texels);
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "%s: host-only context", what);
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_sparse_compact(fmgi_context *c, const void *counts_dev, const fmgi_sparse_info *info, void *sparse_dev,
+                                 void *stream) {
+    const int rc = sparse_call_check(c, counts_dev, sparse_dev, info, "fmgi_sparse_compact");
+    if (rc != FMGI_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    /* count -> the row counts in off[1..B]; scan -> offsets clamped to info->rows; fill */
+    unsigned long long *blob = (unsigned long long *)sparse_dev;
+    HIPCHK(fmgi_launch_sparse_count((const unsigned long long *)counts_dev, c->num_texels, blob, nullptr, s));
+    HIPCHK(fmgi_launch_sparse_scan(blob, info->num_blocks, info->rows, s));
+    HIPCHK(fmgi_launch_sparse_fill((const unsigned long long *)counts_dev, c->num_texels, blob, info->rows, s));
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_sparse_expand(fmgi_context *c, const void *sparse_dev, const fmgi_sparse_info *info, void *counts_dev,
+                                void *stream) {
+    const int rc = sparse_call_check(c, sparse_dev, counts_dev, info, "fmgi_sparse_expand");
+    if (rc != FMGI_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(fmgi_launch_sparse_expand((const unsigned long long *)sparse_dev, c->num_texels, info->rows,
+                                     (unsigned long long *)counts_dev, s));
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_recolour_sparse(fmgi_context *c, const void *const *sparse_dev, const fmgi_sparse_info *infos,
+                                  int num_groups, const fmgi_palette *palettes, int num_scenarios,
+                                  void *const *lm_fx_dev, void *stream) {
+    if (!c || !sparse_dev || !infos || !palettes || !lm_fx_dev || num_groups < 1 || num_scenarios < 1)
+        return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: bad arguments");
+    const int G = num_groups, K = num_scenarios;
+    for (int g = 0; g < G; g++)
+        if (!sparse_dev[g]) return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: blob %d is NULL", g);
+    for (int k = 0; k < K; k++)
+        if (!lm_fx_dev[k]) return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: lightmap %d is NULL", k);
+    for (int64_t i = 0; i < (int64_t)K * G; i++)
+        if (!palette_ok(&palettes[i]))
+            return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: palette of scenario %lld, group %lld outside 0 <= window, "
+                                         "light < 32, 0 <= floor_tint, albedo <= 1", (long long)(i / G), (long long)(i % G));
+    for (int g = 0; g < G; g++)
+        if (const char *f = sparse_info_fault(&infos[g]))
+            return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: group %d: %s", g, f);
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_recolour_sparse: no scene");
+    for (int g = 0; g < G; g++)
+        if (infos[g].num_texels != c->num_texels)
+            return set_err(FMGI_ERR_ARG, "fmgi_recolour_sparse: group %d is of %d texels, the scene has %d", g,
+                           infos[g].num_texels, c->num_texels);
+    std::vector<RecolourLaunch> launches;
+    std::vector<uint32_t> tab;
+    recolour_tables(palettes, G, K, launches, tab);
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "host-only context cannot recolour");
+    if (launches.empty()) return FMGI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int up = recolour_upload(c, tab, s);
+    if (up != FMGI_OK) return up;
+    hipError_t err = hipSuccess;
+    for (const RecolourLaunch &L : launches) {
+        if (infos[L.g].rows == 0) continue; /* an empty histogram */
+        SparseRecolourArgs a;
+        memset(&a, 0, sizeof a);
+        a.blob = (const unsigned long long *)sparse_dev[L.g];
+        a.table = c->d_recolour_tab + L.off;
+        for (int k = 0; k < L.kn; k++) a.lm[k] = (unsigned long long *)lm_fx_dev[L.k0 + k];
+        a.rows = infos[L.g].rows;
+        a.num_texels = c->num_texels;
+        a.k = L.kn;
+        err = fmgi_launch_recolour_sparse(a, s);
+        if (err != hipSuccess) break;
+    }
+    const hipError_t ev = hipEventRecord(c->ev_recolour, s);
+    if (err != hipSuccess) return set_err(FMGI_ERR_HIP, "fmgi_recolour_sparse: %s", hipGetErrorString(err));
+    HIPCHK(ev);
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_sparse_check(const void *sparse_host, size_t bytes, int num_texels, fmgi_sparse_info *info) {
+    if (!sparse_host || !info || num_texels < 1) return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: bad arguments");
+    const int B = fmgi_sparse_blocks(num_texels);
+    if (bytes < 8 * ((size_t)B + 1))
+        return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: truncated: %zu bytes do not cover the %d offsets", bytes, B + 1);
+    const unsigned char *base = (const unsigned char *)sparse_host;
+    auto word = [&](size_t i) { /* no alignment is asked of the host copy */
+        uint64_t v;
+        memcpy(&v, base + 8 * i, 8);
+        return v;
+    };
+    if (word(0) != 0) return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: off[0] is %llu, not 0", (unsigned long long)word(0));
+    for (int b = 0; b < B; b++)
+        if (word((size_t)b + 1) < word(b))
+            return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: off decreases at block %d (%llu after %llu)", b,
+                           (unsigned long long)word((size_t)b + 1), (unsigned long long)word(b));
+    const uint64_t rows = word(B);
+    if (rows > (uint64_t)B * FMGI_COLOUR_STATE_COUNT || bytes != fmgi_sparse_bytes(num_texels, rows))
+        return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: size: %zu bytes, but off[%d] = %llu rows need %llu", bytes, B,
+                       (unsigned long long)rows, (unsigned long long)(8 * ((uint64_t)B + 1) + 512 * rows));
+    uint64_t cells = 0, deposits = 0;
+    const size_t e0 = (size_t)B + 1;
+    for (int b = 0; b < B; b++) {
+        const uint64_t begin = word(b), r = word((size_t)b + 1) - begin;
+        uint64_t most = 0;
+        for (int l = 0; l < 64; l++) {
+            const int64_t t = (int64_t)b * 64 + l;
+            uint64_t n = 0;
+            int last = -1;
+            bool padded = false;
+            for (uint64_t j = 0; j < r; j++) {
+                const uint64_t v = word(e0 + (size_t)(begin + j) * 64 + l);
+                if (v == 0) {
+                    padded = true;
+                    continue;
+                }
+                const int state = (int)(v >> FMGI_SPARSE_COUNT_BITS);
+                if (t >= num_texels)
+                    return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: lane %d of block %d is past the last texel and not "
+                                                 "padding (slot %llu)", l, b, (unsigned long long)j);
+                if (padded)
+                    return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: texel %lld: padding before the cell in slot %llu",
+                                   (long long)t, (unsigned long long)j);
+                if ((v & kSparseCountMask) == 0)
+                    return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: texel %lld: state %d with a count of 0 in slot %llu",
+                                   (long long)t, state, (unsigned long long)j);
+                if (state == last)
+                    return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: texel %lld: duplicate state %d in slot %llu",
+                                   (long long)t, state, (unsigned long long)j);
+                if (state < last)
+                    return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: texel %lld: descending states (%d after %d) in slot "
+                                                 "%llu", (long long)t, state, last, (unsigned long long)j);
+                last = state;
+                n++;
+                deposits += v & kSparseCountMask;
+            }
+            cells += n;
+            most = std::max(most, n);
+        }
+        if (most != r)
+            return set_err(FMGI_ERR_ARG, "fmgi_sparse_check: block %d has %llu rows but no texel uses more than %llu (a "
+                                         "spare row)", b, (unsigned long long)r, (unsigned long long)most);
+    }
+    info->num_texels = num_texels;
+    info->num_blocks = B;
+    info->rows = rows;
+    info->cells = cells;
+    info->deposits = deposits;
+    info->too_large = 0;
     return FMGI_OK;
 }
 

@@ -22,6 +22,7 @@ from . import scene
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
+                   SPARSE_COUNT_BITS, SparseInfo,
                    VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
@@ -70,6 +71,14 @@ __all__ = [
     "FILTER_MAX_MAPS",
     "filter_energy",
     "filter_lightmap",
+    "SparseInfo",
+    "SPARSE_COUNT_BITS",
+    "BAKE_FORMAT",
+    "sparse_bytes",
+    "sparse_check",
+    "scene_hash",
+    "save_bake",
+    "load_bake",
 ]
 
 
@@ -109,6 +118,93 @@ def palette_table(p: Palette) -> np.ndarray:
 def states_bytes(num_texels: int) -> int:
     """Bytes of one histogram, uint64 [1024][num_texels] (fmgi_states_bytes)."""
     return int(load().fmgi_states_bytes(int(num_texels)))
+
+
+def sparse_bytes(num_texels: int, rows: int) -> int:
+    """Bytes of a sparse histogram blob of num_texels texels and `rows` rows (fmgi_sparse_bytes; 0 if
+    num_texels < 1)."""
+    return int(load().fmgi_sparse_bytes(int(num_texels), int(rows)))
+
+
+def sparse_check(blob, num_texels: int) -> SparseInfo:
+    """fmgi_sparse_check: validate a host copy of a sparse histogram blob (bytes, or an array whose bytes are
+    the blob) of num_texels texels; returns its SparseInfo. Raises FmgiError naming the first violation."""
+    raw = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview))
+                               else np.asarray(blob)).view(np.uint8).reshape(-1)
+    info = SparseInfo()
+    buf = raw if len(raw) else np.zeros(1, np.uint8)
+    check(load().fmgi_sparse_check(buf.ctypes.data_as(C.c_void_p), len(raw), int(num_texels), C.byref(info)),
+          "fmgi_sparse_check")
+    return info
+
+
+BAKE_FORMAT = "fmgi-bake-1"
+
+
+def scene_hash(sc: Scene) -> str:
+    """SHA-256 (hex) over the scene's walls, windows and lights bytes and its texel count: what a saved bake is
+    tied to."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for a in (sc.walls, sc.windows, sc.lights):
+        h.update(np.ascontiguousarray(a).tobytes())
+    h.update(np.int64(sc.num_texels).tobytes())
+    return h.hexdigest()
+
+
+def save_bake(path, sc: Scene, spa: int, wg: int, launches: np.ndarray, groups):
+    """Write a traced scene as one .npz: the format tag, the scene's hash, spa, wg, the plan's launches
+    (Context.get_plan()) and per group its label, item range, is_window, rows and sparse blob. groups: a list of
+    (label, item_begin, item_end, is_window, blob) with blob a uint64 array (a host copy of the device blob). Every
+    blob is checked (sparse_check) before anything is written."""
+    launches = np.ascontiguousarray(launches, LAUNCH_DTYPE)
+    out = {"format": np.array(BAKE_FORMAT), "scene_sha256": np.array(scene_hash(sc)),
+           "num_texels": np.int64(sc.num_texels), "spa": np.int64(spa), "wg": np.int64(wg),
+           "launches": launches.view(np.uint8).reshape(-1).copy(),
+           "labels": np.array([str(g[0]) for g in groups], dtype=np.str_),
+           "ranges": np.array([[int(g[1]), int(g[2])] for g in groups], np.uint64).reshape(len(groups), 2),
+           "is_window": np.array([bool(g[3]) for g in groups], np.uint8)}
+    rows = []
+    for i, g in enumerate(groups):
+        blob = np.ascontiguousarray(g[4], np.uint64).reshape(-1)
+        rows.append(sparse_check(blob, sc.num_texels).rows)
+        out[f"blob_{i}"] = blob
+    out["rows"] = np.array(rows, np.uint64)
+    with open(path, "wb") as f:
+        np.savez(f, **out)
+
+
+def load_bake(path, sc: Scene | None = None) -> dict:
+    """Read a save_bake file (allow_pickle=False). Returns {"spa", "wg", "num_texels", "scene_sha256", "launches"
+    (LAUNCH_DTYPE), "groups": [{"label", "item_begin", "item_end", "is_window", "rows", "info" (SparseInfo),
+    "blob" (uint64)}]}. Every blob passes sparse_check. ValueError for a wrong format tag, a scene hash that
+    differs from `sc`'s (when sc is given) or a blob that fails its check."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or str(z["format"]) != BAKE_FORMAT:
+            tag = str(z["format"]) if "format" in z.files else None
+            raise ValueError(f"{path}: format tag {tag!r}, not {BAKE_FORMAT!r}")
+        d = {k: z[k] for k in z.files}
+    sha, T = str(d["scene_sha256"]), int(d["num_texels"])
+    if sc is not None and (sha != scene_hash(sc) or T != sc.num_texels):
+        raise ValueError(f"{path}: baked for another scene (file {sha[:12]}..., {T} texels; scene {sc.name!r} "
+                         f"{scene_hash(sc)[:12]}..., {sc.num_texels} texels)")
+    launches = np.ascontiguousarray(d["launches"], np.uint8)
+    if len(launches) % LAUNCH_DTYPE.itemsize:
+        raise ValueError(f"{path}: {len(launches)} bytes of launches are no whole number of launches")
+    groups = []
+    for i, label in enumerate(d["labels"].tolist()):
+        blob = np.ascontiguousarray(d[f"blob_{i}"], np.uint64).reshape(-1)
+        try:
+            info = sparse_check(blob, T)
+        except FmgiError as e:
+            raise ValueError(f"{path}: group {label!r}: {e}") from None
+        if info.rows != int(d["rows"][i]):
+            raise ValueError(f"{path}: group {label!r}: {info.rows} rows in the blob, {int(d['rows'][i])} recorded")
+        groups.append({"label": str(label), "item_begin": int(d["ranges"][i][0]), "item_end": int(d["ranges"][i][1]),
+                       "is_window": bool(d["is_window"][i]), "rows": int(info.rows), "info": info, "blob": blob})
+    return {"spa": int(d["spa"]), "wg": int(d["wg"]), "num_texels": T, "scene_sha256": sha,
+            "launches": launches.view(LAUNCH_DTYPE).copy(), "groups": groups}
 
 
 def filter_energy(deposits: int, palette: Palette | None = None) -> int:
@@ -250,6 +346,49 @@ class Context:
             for g, p in enumerate(row):
                 C.memmove(C.byref(pal, (k * G + g) * C.sizeof(Palette)), C.byref(p), C.sizeof(Palette))
         check(self.lib.fmgi_recolour(self.h, cp, G, pal, K, lp, C.c_void_p(stream or None)), "fmgi_recolour")
+
+    def sparse_measure(self, counts_ptr: int, stream: int = 0) -> SparseInfo:
+        """fmgi_sparse_measure: one pass over the device histogram at counts_ptr; synchronises `stream` and returns
+        its SparseInfo (rows sizes the blob: sparse_bytes(num_texels, info.rows)). Raises FmgiError if a count is
+        2^54 or more."""
+        info = SparseInfo()
+        check(self.lib.fmgi_sparse_measure(self.h, C.c_void_p(counts_ptr or None), C.byref(info),
+                                           C.c_void_p(stream or None)), "fmgi_sparse_measure")
+        return info
+
+    def sparse_compact(self, counts_ptr: int, info: SparseInfo, sparse_ptr: int, stream: int = 0):
+        """fmgi_sparse_compact: the device histogram at counts_ptr into its sparse blob at sparse_ptr
+        (sparse_bytes(num_texels, info.rows) bytes; info from sparse_measure). Asynchronous on `stream`."""
+        check(self.lib.fmgi_sparse_compact(self.h, C.c_void_p(counts_ptr or None), C.byref(info),
+                                           C.c_void_p(sparse_ptr or None), C.c_void_p(stream or None)),
+              "fmgi_sparse_compact")
+
+    def sparse_expand(self, sparse_ptr: int, info: SparseInfo, counts_ptr: int, stream: int = 0):
+        """fmgi_sparse_expand: adds the blob at sparse_ptr to the device histogram uint64 [1024][num_texels] at
+        counts_ptr. Asynchronous on `stream`."""
+        check(self.lib.fmgi_sparse_expand(self.h, C.c_void_p(sparse_ptr or None), C.byref(info),
+                                          C.c_void_p(counts_ptr or None), C.c_void_p(stream or None)),
+              "fmgi_sparse_expand")
+
+    def recolour_sparse(self, sparse_ptrs, infos, palettes, lm_ptrs, stream: int = 0):
+        """fmgi_recolour_sparse: recolour() on sparse blobs: lm[k] += the blobs sparse_ptrs[g] (with infos[g])
+        folded with palettes[k][g], exactly. Asynchronous on `stream`."""
+        G, K = len(sparse_ptrs), len(lm_ptrs)
+        if len(infos) != G:
+            raise FmgiError(f"recolour_sparse: {G} blobs, {len(infos)} infos")
+        if len(palettes) != K or any(len(row) != G for row in palettes):
+            raise FmgiError(f"recolour_sparse: palettes must be {K} scenarios x {G} groups")
+        sp = (C.c_void_p * max(G, 1))(*[C.c_void_p(int(p)) for p in sparse_ptrs])
+        lp = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p)) for p in lm_ptrs])
+        inf = (SparseInfo * max(G, 1))()
+        for g, i in enumerate(infos):
+            C.memmove(C.byref(inf, g * C.sizeof(SparseInfo)), C.byref(i), C.sizeof(SparseInfo))
+        pal = (Palette * max(K * G, 1))()
+        for k, row in enumerate(palettes):
+            for g, p in enumerate(row):
+                C.memmove(C.byref(pal, (k * G + g) * C.sizeof(Palette)), C.byref(p), C.sizeof(Palette))
+        check(self.lib.fmgi_recolour_sparse(self.h, sp, inf, G, pal, K, lp, C.c_void_p(stream or None)),
+              "fmgi_recolour_sparse")
 
     def filter_radii(self, guide_ptr: int, min_energy: int, max_radius: int, radii_ptr: int, stream: int = 0):
         """fmgi_filter_radii: per level-0 texel the smallest window radius in [0, max_radius] that holds

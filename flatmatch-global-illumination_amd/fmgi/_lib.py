@@ -75,6 +75,12 @@ EXPORTS = (
     "fmgi_states_bytes",
     "fmgi_bake_states",
     "fmgi_recolour",
+    "fmgi_sparse_bytes",
+    "fmgi_sparse_measure",
+    "fmgi_sparse_compact",
+    "fmgi_sparse_expand",
+    "fmgi_recolour_sparse",
+    "fmgi_sparse_check",
     "fmgi_filter_energy",
     "fmgi_filter_radii",
     "fmgi_filter_apply",
@@ -95,6 +101,7 @@ VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
 COLOUR_STATE_COUNT = 1024
 RECOLOUR_MAX_SCENARIOS = 8
+SPARSE_COUNT_BITS = 54
 FILTER_MAX_RADIUS = 16
 FILTER_MAX_MAPS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
@@ -206,6 +213,33 @@ class Palette(C.Structure):
 assert C.sizeof(Palette) == 40
 
 
+class SparseInfo(C.Structure):
+    """fmgi_sparse_info (include/flatmatch_gi.h): the size and the sums of one sparse histogram blob."""
+
+    _fields_ = [
+        ("num_texels", C.c_int32),
+        ("num_blocks", C.c_int32),
+        ("rows", C.c_uint64),
+        ("cells", C.c_uint64),
+        ("deposits", C.c_uint64),
+        ("too_large", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __eq__(self, other):
+        return isinstance(other, SparseInfo) and self.as_dict() == other.as_dict()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"SparseInfo({', '.join(f'{k}={v}' for k, v in self.as_dict().items())})"
+
+
+assert C.sizeof(SparseInfo) == 40
+
+
 class Geometry(C.Structure):
     """geometry.h:7-15 (80 B)."""
 
@@ -302,6 +336,12 @@ def load() -> C.CDLL:
         "fmgi_states_bytes": (C.c_size_t, [C.c_int]),
         "fmgi_bake_states": (C.c_int, [vp, u64, u64, vp, C.c_int, vp]),
         "fmgi_recolour": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+        "fmgi_sparse_bytes": (C.c_size_t, [C.c_int, u64]),
+        "fmgi_sparse_measure": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp]),
+        "fmgi_sparse_compact": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp, vp]),
+        "fmgi_sparse_expand": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp, vp]),
+        "fmgi_recolour_sparse": (C.c_int, [vp, vp, C.POINTER(SparseInfo), C.c_int, vp, C.c_int, vp, vp]),
+        "fmgi_sparse_check": (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(SparseInfo)]),
         "fmgi_filter_energy": (u64, [C.POINTER(Palette), u64]),
         "fmgi_filter_radii": (C.c_int, [vp, vp, u64, C.c_int, vp, vp]),
         "fmgi_filter_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),

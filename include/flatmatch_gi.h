@@ -343,6 +343,62 @@ int fmgi_bake_states(fmgi_context *ctx, uint64_t item_begin, uint64_t item_end, 
 int fmgi_recolour(fmgi_context *ctx, const void *const *counts_dev, int num_groups, const fmgi_palette *palettes,
                   int num_scenarios, void *const *lm_fx_dev, void *stream);
 
+/* ---- Sparse photon histograms: compact, recolour, expand, check --------------------- */
+/* The sparse, blocked form of one histogram. T = numTexels, B = (T + 63) / 64 blocks of 64 consecutive texels.
+   One blob of uint64 words (this layout is what files hold):
+     off[B + 1]        off[0] = 0; off[b + 1] - off[b] = r_b, the largest number of non-zero states any texel of
+                       block b has; rows = off[B]
+     entry[64 * rows]  slot j (0 <= j < r_b) of texel t = 64 b + l is entry[(off[b] + j) * 64 + l] and holds
+                       (state << 54) | count for the texel's j-th non-zero state in ascending state order, or 0
+                       (padding) when the texel has fewer than j + 1 non-zero states or t >= T
+   so a wave reading row off[b] + j reads 512 contiguous bytes; 8 (B + 1) + 512 rows bytes in all. Counts must be
+   below 2^54. The form is canonical: a histogram has exactly one blob, bit for bit. */
+#define FMGI_SPARSE_COUNT_BITS 54
+typedef struct fmgi_sparse_info {
+    int32_t num_texels, num_blocks;   /* num_blocks == (num_texels + 63) / 64 */
+    uint64_t rows;                    /* off[num_blocks] */
+    uint64_t cells;                   /* non-zero (state, texel) cells */
+    uint64_t deposits;                /* sum of the counts mod 2^64 */
+    uint64_t too_large;               /* cells whose count is >= 2^54 */
+} fmgi_sparse_info;
+/* Host only: bytes of a blob of num_texels texels and `rows` rows (0 if num_texels < 1). */
+size_t fmgi_sparse_bytes(int num_texels, uint64_t rows);
+/* The device calls below check their arguments on the host before any device call, in this order: FMGI_ERR_ARG
+   for a NULL context or pointer (and num_groups < 1, num_scenarios < 1, a rejected palette), or an info with
+   num_blocks != (num_texels + 63) / 64 or too_large != 0; FMGI_ERR_STATE without a scene; FMGI_ERR_ARG if
+   info.num_texels is not the scene's texel count; FMGI_ERR_NO_DEVICE on a host-only context. Every kernel that
+   reads a blob takes info.rows from the host, clamps each block's [off[b], off[b + 1]) to [0, rows] and skips a
+   block whose begin exceeds its end; the state field has 10 bits. So a device blob of
+   fmgi_sparse_bytes(T, info.rows) bytes cannot cause an access out of bounds, whatever it holds. */
+/* One pass over the dense histogram counts_dev of the current scene's texel count: synchronises `stream` and
+   fills *info. FMGI_ERR_ARG, with *info still filled, if too_large != 0. */
+int fmgi_sparse_measure(fmgi_context *ctx, const void *counts_dev, fmgi_sparse_info *info, void *stream);
+/* Writes the histogram's blob, fmgi_sparse_bytes(T, info->rows) bytes, to sparse_dev. Asynchronous. The offsets
+   are recomputed (count, scan, fill; nothing of fmgi_sparse_measure is kept in the context) and clamped to
+   info->rows, and a lane never writes outside its block's clamped rows: if the histogram changed since it was
+   measured the blob is unspecified, but no byte outside the buffer is written. */
+int fmgi_sparse_compact(fmgi_context *ctx, const void *counts_dev, const fmgi_sparse_info *info, void *sparse_dev,
+                        void *stream);
+/* counts_dev[state][t] += count for every non-padding entry, each texel's rows in order (no atomics; defined
+   for duplicate entries too): expanding a compacted histogram into zeros gives the histogram. Asynchronous. */
+int fmgi_sparse_expand(fmgi_context *ctx, const void *sparse_dev, const fmgi_sparse_info *info, void *counts_dev,
+                       void *stream);
+/* fmgi_recolour on blobs: lm_fx[k][t][c] += sum over groups g and g's entries of texel t of
+   count * table(palettes[k * num_groups + g])[state][c], in exact 64-bit integers mod 2^64; .s[3] is not
+   touched. sparse_dev[num_groups] with infos[num_groups]; any number of scenarios, in passes of
+   FMGI_RECOLOUR_MAX_SCENARIOS; a group whose table is zero in a whole pass is not read. A wave owns its 64
+   texels and adds without atomics: the groups are launches of one stream, and nothing else may add to the
+   lightmaps meanwhile. Asynchronous; the palettes are read before the call returns. */
+int fmgi_recolour_sparse(fmgi_context *ctx, const void *const *sparse_dev, const fmgi_sparse_info *infos,
+                         int num_groups, const fmgi_palette *palettes, int num_scenarios, void *const *lm_fx_dev,
+                         void *stream);
+/* Host only: validates a host copy of a blob (what a loader calls before uploading) and fills *info. Checks that
+   bytes covers off[], off[0] == 0, off[] does not decrease, bytes == fmgi_sparse_bytes(num_texels, off[B]); per
+   texel that non-zero entries have strictly ascending state, padding comes only after them and lanes t >= T are
+   all padding; and that every block has a texel that uses all its rows. FMGI_ERR_ARG otherwise, with
+   fmgi_last_error naming the first violation. info->too_large is 0 (a count field cannot hold more). */
+int fmgi_sparse_check(const void *sparse_host, size_t bytes, int num_texels, fmgi_sparse_info *info);
+
 /* ---- Adaptive density filter for noisy, low-photon lightmaps ------------------------ */
 /* A radiance estimate on the binned photons: per level-0 texel a square window, grown until it holds enough
    deposit energy and clipped to the texel's own wall, then the mean over that window. No reference counterpart.

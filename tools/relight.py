@@ -25,7 +25,17 @@ filter before it is finalised: per texel a window of radius <= 
 holds the energy of N first-bounce window photons in the reference-palette lightmap of all groups, so all
 scenarios share one radius map.
 
+With --sparse every group's histogram is compacted into its sparse, blocked form as soon as it is
+traced, through one reused dense scratch histogram, and the scenarios are folded from the sparse blobs
+(fmgi.Context.recolour_sparse): one dense histogram plus the blobs of device memory instead of one dense histogram
+per group, the same lightmaps bit for bit. --save-bake FILE (implies --sparse) writes the traced scene to one .npz
+(fmgi.save_bake); --load-bake FILE lights it again without tracing anything: --spa is then optional (it is taken
+from the file and must agree if given) and --per-light follows the file's groups. A file baked for another scene is
+refused before any device is touched.
+
   python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --scenarios scenarios.json -o out
+  python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --per-light --save-bake example.npz --scenarios a.json
+  python tools/relight.py tests/golden/example_geometry.bin --load-bake example.npz --scenarios b.json -o out_b
   python tools/relight.py tests/golden/example_geometry.bin --spa 65000 --min-deposits 256 --scenarios scenarios.json
 """
 import argparse
@@ -104,7 +114,7 @@ def parse_args(argv=None):
     ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
     ap.add_argument("--tile-size", type=float, default=None, help="box scenes: lightmap texels per m^2 (default 200)")
     ap.add_argument("--with-light", action="store_true", help="box scenes: add the ceiling light")
-    ap.add_argument("--spa", type=int, required=True, help="numSamplesPerArea of the bake")
+    ap.add_argument("--spa", type=int, default=None, help="numSamplesPerArea of the bake (optional with --load-bake)")
     ap.add_argument("--scenarios", required=True, help="JSON file: a list of {name, windows, lights}")
     ap.add_argument("--per-light", action="store_true", help="one histogram per light instead of one for all")
     ap.add_argument("--offsets", default=None, help=".npy of int32 launch offsets (default: libc rand(), as the reference)")
@@ -125,7 +135,17 @@ def parse_args(argv=None):
                     help="adaptive density filter: grow every texel's window until it holds the energy of N "
                          "first-bounce window photons (default 0: no filter)")
     ap.add_argument("--max-radius", type=int, default=4, help="the filter's largest window radius in texels (0..16)")
+    ap.add_argument("--sparse", action="store_true",
+                    help="compact every group's histogram into its sparse form and recolour from the blobs")
+    ap.add_argument("--save-bake", default=None, metavar="FILE", help="write the traced scene to FILE (implies --sparse)")
+    ap.add_argument("--load-bake", default=None, metavar="FILE", help="light the bake of FILE: nothing is traced")
     a = ap.parse_args(argv)
+    if a.load_bake is None and a.spa is None:
+        ap.error("the following arguments are required: --spa")
+    if a.load_bake is not None and a.save_bake is not None:
+        ap.error("--save-bake with --load-bake: the file already exists")
+    if a.save_bake is not None or a.load_bake is not None:
+        a.sparse = True
     if a.min_deposits < 0:
         ap.error("--min-deposits must not be negative")
     if not 0 <= a.max_radius <= 16:
@@ -147,11 +167,24 @@ def main(argv=None):
     if len(set(names)) != len(names) or any(os.sep in n or n in ("", ".", "..") for n in names):
         sys.exit(f"{a.scenarios}: scenario names must be distinct directory names")
     sc = load_scene(a.scene, a.tile_size, a.with_light)
+    loaded = None
+    if a.load_bake is not None:  # every mismatch ends the run here, before a device context exists
+        try:
+            loaded = fmgi.load_bake(a.load_bake, sc)
+        except (ValueError, OSError) as e:
+            sys.exit(f"--load-bake: {e}")
+        if a.spa is not None and a.spa != loaded["spa"]:
+            sys.exit(f"--load-bake: {a.load_bake} was baked with --spa {loaded['spa']}, not {a.spa}")
+        a.spa = loaded["spa"]
     dev = f"cuda:{a.device}"
     ctx = fmgi.Context(a.device)
     ctx.set_scene(sc)
-    items = ctx.plan(a.spa, rng_offsets=None if a.offsets is None else np.load(a.offsets))
-    groups = source_groups(ctx.source_ranges(), a.per_light)
+    if loaded is None:
+        items = ctx.plan(a.spa, rng_offsets=None if a.offsets is None else np.load(a.offsets))
+        groups = source_groups(ctx.source_ranges(), a.per_light)
+    else:
+        items = int(loaded["launches"]["count"].sum())
+        groups = [(g["label"], g["item_begin"], g["item_end"], g["is_window"]) for g in loaded["groups"]]
     if not groups:
         sys.exit("the scene has no windows and no lights")
     palettes = [scenario_palettes(e, groups) for e in entries]
@@ -160,15 +193,39 @@ def main(argv=None):
     T = sc.num_texels
     s = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(s):
-        hists = [torch.zeros((fmgi.COLOUR_STATE_COUNT, T), dtype=torch.int64, device=dev) for _ in groups]
-        for h, (_, b, e, _) in zip(hists, groups):
-            ctx.bake_states(b, e, h.data_ptr(), kernel, s.cuda_stream)
+        if loaded is not None:
+            infos = [g["info"] for g in loaded["groups"]]
+            blobs = [torch.from_numpy(g["blob"].view(np.int64)).to(dev) for g in loaded["groups"]]
+        elif a.sparse:
+            # one dense scratch histogram for every group in turn: bake, measure, compact, zero
+            scratch = torch.zeros((fmgi.COLOUR_STATE_COUNT, T), dtype=torch.int64, device=dev)
+            infos, blobs = [], []
+            for _, b, e, _ in groups:
+                ctx.bake_states(b, e, scratch.data_ptr(), kernel, s.cuda_stream)
+                info = ctx.sparse_measure(scratch.data_ptr(), s.cuda_stream)
+                blob = torch.empty(fmgi.sparse_bytes(T, info.rows) // 8, dtype=torch.int64, device=dev)
+                ctx.sparse_compact(scratch.data_ptr(), info, blob.data_ptr(), s.cuda_stream)
+                scratch.zero_()
+                infos.append(info)
+                blobs.append(blob)
+            del scratch
+        else:
+            hists = [torch.zeros((fmgi.COLOUR_STATE_COUNT, T), dtype=torch.int64, device=dev) for _ in groups]
+            for h, (_, b, e, _) in zip(hists, groups):
+                ctx.bake_states(b, e, h.data_ptr(), kernel, s.cuda_stream)
+
+        def recolour(pals, lm_ptrs):
+            if a.sparse:
+                ctx.recolour_sparse([b.data_ptr() for b in blobs], infos, pals, lm_ptrs, s.cuda_stream)
+            else:
+                ctx.recolour([h.data_ptr() for h in hists], pals, lm_ptrs, s.cuda_stream)
+
         lms = [torch.zeros((T, 4), dtype=torch.int64, device=dev) for _ in entries]
-        ctx.recolour([h.data_ptr() for h in hists], palettes, [lm.data_ptr() for lm in lms], s.cuda_stream)
+        recolour(palettes, [lm.data_ptr() for lm in lms])
         if a.min_deposits > 0:
             # one radius map for every scenario, from the photon density: the reference-palette lightmap of all groups
             guide = torch.zeros((T, 4), dtype=torch.int64, device=dev)
-            ctx.recolour([h.data_ptr() for h in hists], [[fmgi.Palette()] * len(groups)], [guide.data_ptr()], s.cuda_stream)
+            recolour([[fmgi.Palette()] * len(groups)], [guide.data_ptr()])
             radii = torch.zeros(T, dtype=torch.uint8, device=dev)
             ctx.filter_radii(guide.data_ptr(), fmgi.filter_energy(a.min_deposits), a.max_radius, radii.data_ptr(),
                              s.cuda_stream)
@@ -179,8 +236,22 @@ def main(argv=None):
         for lm, t in zip(lms, texels):
             ctx.finalize(lm.data_ptr(), zero.data_ptr(), t.data_ptr(), s.cuda_stream)
     s.synchronize()
-    print(f"{sc.name}: {100 * items} photons, {T} texels, {len(groups)} histograms of "
-          f"{fmgi.states_bytes(T) / 2**20:.1f} MiB ({', '.join(g[0] for g in groups)}), {len(entries)} scenarios")
+    if a.save_bake is not None:
+        fmgi.save_bake(a.save_bake, sc, a.spa, 256, ctx.get_plan(),
+                       [(g[0], g[1], g[2], g[3], b.cpu().numpy().view(np.uint64)) for g, b in zip(groups, blobs)])
+    if not a.sparse:
+        print(f"{sc.name}: {100 * items} photons, {T} texels, {len(groups)} histograms of "
+              f"{fmgi.states_bytes(T) / 2**20:.1f} MiB ({', '.join(g[0] for g in groups)}), {len(entries)} scenarios")
+    else:
+        sizes = [fmgi.sparse_bytes(T, i.rows) for i in infos]
+        cells, slots = sum(i.cells for i in infos), 64 * sum(i.rows for i in infos)
+        traced = (f"loaded from {a.load_bake}, 0 items traced" if loaded is not None else f"{items} items traced")
+        print(f"{sc.name}: {100 * items} photons ({traced}), {T} texels, {len(groups)} sparse histograms of "
+              f"{', '.join(f'{g[0]} {n / 2**20:.2f} MiB' for g, n in zip(groups, sizes))} "
+              f"({100.0 * sum(sizes) / (len(groups) * fmgi.states_bytes(T)):.1f} % of dense, fill "
+              f"{cells / max(slots, 1):.2f}), {len(entries)} scenarios")
+        if a.save_bake is not None:
+            print(f"  bake saved to {a.save_bake}: {os.path.getsize(a.save_bake)} bytes")
     if a.min_deposits > 0:
         print(f"  filtered: {a.min_deposits} deposits, radius <= {a.max_radius}, mean radius "
               f"{radii.float().mean().item():.3f}")
