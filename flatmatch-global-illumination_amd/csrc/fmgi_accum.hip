@@ -786,6 +786,23 @@ int fmgi_fold_split(int tb) {
     return got;
 }
 
+/* the bucket layouts' pool blocks listed by tile: sb.tile_blocks[0, P) = every tile's block count, sb.block_list =
+   the block ids, each tile's contiguous in tile order (k_bucket_count, k_bucket_list); the fold's first step, and
+   what the histogram pass of fmgi_bake_sparse walks (fmgi_hist.hip) */
+hipError_t fmgi_stream_bucket_list(const StreamBufs &sb, int num_texels, hipStream_t s) {
+    const int tb = sb.tile_bits > 0 ? sb.tile_bits : FMGI_TILE_BITS;
+    const int P = (num_texels + (1 << tb) - 1) >> tb;
+    const unsigned lg = (unsigned)((sb.pool_blocks + (uint64_t)kListThreads * kListPerThread - 1) /
+                                   ((uint64_t)kListThreads * kListPerThread));
+    hipError_t e = hipMemsetAsync(sb.tile_blocks, 0, 2 * (FMGI_PRESORT_MAX_TILES + 1) * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bucket_count, dim3(lg), dim3(kListThreads), 0, s, sb.block_tile, sb.cursor, sb.pool_blocks,
+                       P, sb.tile_blocks);
+    hipLaunchKernelGGL(k_bucket_list, dim3(lg), dim3(kListThreads), 0, s, sb.block_tile, sb.cursor, sb.pool_blocks, P,
+                       sb.tile_blocks, sb.tile_blocks + FMGI_PRESORT_MAX_TILES + 1, sb.block_list);
+    return hipGetLastError();
+}
+
 hipError_t fmgi_stream_fold(const StreamBufs &sb, int num_texels, unsigned long long *lm, hipStream_t s) {
     /* the bucket layouts' tiles may be wide (sb.tile_bits); the others are FMGI_TILE_BITS */
     const int tb = sb.presort >= 2 && sb.tile_bits > 0 ? sb.tile_bits : FMGI_TILE_BITS;
@@ -809,14 +826,8 @@ hipError_t fmgi_stream_fold(const StreamBufs &sb, int num_texels, unsigned long 
 #endif
     if (sb.presort >= 2) {
         /* the blocks listed by tile (counts, then each workgroup's range in its tiles' parts), then the sums */
-        const unsigned lg = (unsigned)((sb.pool_blocks + (uint64_t)kListThreads * kListPerThread - 1) /
-                                       ((uint64_t)kListThreads * kListPerThread));
-        hipError_t e = hipMemsetAsync(sb.tile_blocks, 0, 2 * (FMGI_PRESORT_MAX_TILES + 1) * sizeof(uint32_t), s);
+        hipError_t e = fmgi_stream_bucket_list(sb, num_texels, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_bucket_count, dim3(lg), dim3(kListThreads), 0, s, sb.block_tile, sb.cursor, sb.pool_blocks,
-                           P, sb.tile_blocks);
-        hipLaunchKernelGGL(k_bucket_list, dim3(lg), dim3(kListThreads), 0, s, sb.block_tile, sb.cursor, sb.pool_blocks, P,
-                           sb.tile_blocks, sb.tile_blocks + FMGI_PRESORT_MAX_TILES + 1, sb.block_list);
         typedef void (*FoldFn)(const uint32_t *, const uint32_t *, const uint32_t *, const uint32_t *, int, int, int,
                                const uint4 *, unsigned long long *, int);
         /* the channels summed as u32 low words with carry words (CARRY >= 2): box200's wide fold 11.76 -> 11.54 ms,

@@ -35,6 +35,7 @@
 #include "fmgi_filter.h"
 #include "fmgi_recolour.h"
 #include "fmgi_sparse.h"
+#include "fmgi_hist.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
 
@@ -932,7 +933,7 @@ struct fmgi_context {
     std::string last_kernel; /* fmgi_last_bake_kernel: the instance(s) the last bake launch ran */
     int grid_cpr = 0; /* fmgi_set_grid_cells_per_record: the grid's cells per record (0: the product's choice) */
     /* fmgi_set_option: the tests' handles on product paths a given scene would not take (include/flatmatch_gi.h) */
-    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0, -1, -1};
+    int64_t opt[FMGI_OPT_COUNT] = {0, 0, 0, -1, -1, -1, 0, 0, -1, -1, 0};
     /* the closed box's six verified lattice descriptors (build_lattice; fmgi_lattice_copy), in the plane image's
        order and uploaded after it in d_gimg; empty: the scene has no lattice */
     std::vector<LatticeDesc> h_lattice;
@@ -941,7 +942,30 @@ struct fmgi_context {
     std::vector<ClassC> h_classc;
     std::vector<float> h_recf;     /* {cu, hwu, cv, hwv} by rect index, then the dummy */
     std::vector<uint32_t> h_cellc; /* two u32 per cell: idx0 | idx1 << 16, idx2 | idx3 << 16 */
+    /* fmgi_bake_sparse / fmgi_sparse_from_codes: the held result (a canonical blob and its info);
+       hist_on makes bake_common's STREAM chunks count their codes into it instead of folding them into the
+       lightmap (hist_kernel: the caller's kernel id, for a chunk's dense route); the call's stats and its device
+       bytes (now, peak); the scratch lightmap the bake's bucket fallback adds to (nobody reads it) and the copy
+       of the device stats taken before every chunk */
+    unsigned long long *hist_blob = nullptr;
+    fmgi_sparse_info hist_info{};
+    bool hist_held = false, hist_on = false;
+    int hist_kernel = FMGI_KERNEL_AUTO;
+    fmgi_bake_sparse_stats hist_stats{};
+    size_t hist_bytes = 0;
+    unsigned long long *d_hist_lm = nullptr;
+    unsigned long long *d_hist_stats = nullptr;
 };
+
+/* releases the held sparse histogram and the scratch lightmap of fmgi_bake_sparse (hipFree waits for the device) */
+static void hist_release(fmgi_context *c) {
+    c->hist_held = false;
+    if (c->device == FMGI_HOST_ONLY || (!c->hist_blob && !c->d_hist_lm)) return;
+    if (hipSetDevice(c->device) != hipSuccess) return;
+    (void)hipFree(c->hist_blob);
+    (void)hipFree(c->d_hist_lm);
+    c->hist_blob = c->d_hist_lm = nullptr;
+}
 
 /* the closed-box (one plane per axis and class) instances off: FMGI_OPT_NO_AXES (tests; at fmgi_set_scene) */
 static bool no_axes(const fmgi_context *c) { return c->opt[FMGI_OPT_NO_AXES] != 0 || fmgi_exp_env("FMGI_NO_AXES"); }
@@ -1031,6 +1055,9 @@ FMGI_API void fmgi_destroy(fmgi_context *c) {
     if (c->ev_recolour) { hipEventSynchronize(c->ev_recolour); hipEventDestroy(c->ev_recolour); }
     hipFree(c->d_recolour_tab);
     hipFree(c->d_sparse_sums);
+    hipFree(c->hist_blob);
+    hipFree(c->d_hist_lm);
+    hipFree(c->d_hist_stats);
     if (c->ev_filter) { hipEventSynchronize(c->ev_filter); hipEventDestroy(c->ev_filter); }
     hipFree(c->d_filter_tex);
     hipFree(c->d_filter_walls);
@@ -1677,6 +1704,7 @@ FMGI_API int fmgi_set_scene(fmgi_context *c, const fmgi_rect *walls, int num_wal
     HIPCHK(upload(&c->d_grecs, gb.recs));
     HIPCHK(upload(&c->d_gidx, gb.idx));
     }
+    hist_release(c); /* a held sparse histogram is of the previous scene */
     c->num_texels = num_texels;
     /* the filter's grids change with the texel count, also when a step below fails: its tables are rebuilt */
     c->h_wall_lm.resize((size_t)num_walls * 3);
@@ -2095,6 +2123,8 @@ static int exec_accum(const fmgi_context *c) {
     const size_t tables = (size_t)c->nrects * sizeof(RectLds) + (c->cells_lds ? (size_t)c->grid_cells * sizeof(GridCell) : 0);
     return tables <= 64 * 1024 ? kAccScatter : kAccBucket;
 }
+
+static int hist_chunk(fmgi_context *c, const StreamBufs &sb, uint64_t cb, uint64_t ce, hipStream_t s);
 
 static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int kernel, hipStream_t s, bool trace,
                        void *events, int32_t *counts, uint32_t *rngf) {
@@ -2554,6 +2584,9 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
             a.stream_cursor = sb.cursor + 1;
         }
         HIPCHK(fetch_table(cb, ce));
+        if (c->hist_on) /* fmgi_bake_sparse: the device stats as they are before this chunk */
+            HIPCHK(hipMemcpyAsync(c->d_hist_stats, c->d_stats, KSTAT_ALLOC * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemsetAsync(c->d_counter, 0, 8, s));
         HIPCHK(hipMemsetAsync(sb.cursor, 0, 16, s)); /* the pool / stream cursor and the dense stream's */
         hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -2622,7 +2655,12 @@ static int bake_common(fmgi_context *c, uint64_t b, uint64_t e, void *lm, int ke
             HIPCHK(hipStreamWaitEvent(fs, c->ev_baked[k], 0));
         }
         HIPCHK(time_begin(c, fs, t0));
-        HIPCHK(fmgi_stream_fold(sb, c->num_texels, (unsigned long long *)lm, fs));
+        if (c->hist_on) { /* fmgi_bake_sparse: the chunk's codes counted into the held histogram, no lightmap */
+            rc = hist_chunk(c, sb, cb, ce, fs);
+            if (rc != FMGI_OK) return rc;
+        } else {
+            HIPCHK(fmgi_stream_fold(sb, c->num_texels, (unsigned long long *)lm, fs));
+        }
         HIPCHK(time_end(c, fs, t0, t1, c->ev_fold));
         if (overlap) HIPCHK(hipEventRecord(c->ev_folded[k], fs));
     }
@@ -3053,6 +3091,515 @@ FMGI_API int fmgi_sparse_check(const void *sparse_host, size_t bytes, int num_te
     info->cells = cells;
     info->deposits = deposits;
     info->too_large = 0;
+    return FMGI_OK;
+}
+
+/* ---- sparse histograms from deposit codes; the sum of two blobs ---- */
+
+static const uint64_t kHistBatchCodes = 64ull << 20; /* codes per counting batch: a 256-MB scratch */
+static const int kHistDense = 1;                      /* hist_build: the codes need the dense route */
+
+/* device memory of the sparse-bake path, counted in fmgi_bake_sparse_stats.scratch_bytes */
+static int hist_malloc(fmgi_context *c, void **p, size_t bytes, const char *what) {
+    *p = nullptr;
+    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return set_err(FMGI_ERR_OOM, "sparse bake: no device memory for %s (%zu bytes)", what, bytes);
+    }
+    c->hist_bytes += bytes;
+    c->hist_stats.scratch_bytes = std::max<uint64_t>(c->hist_stats.scratch_bytes, c->hist_bytes);
+    return FMGI_OK;
+}
+static void hist_free(fmgi_context *c, void *p, size_t bytes) {
+    if (!p) return;
+    (void)hipFree(p); /* (waits for the device: no launch still uses it) */
+    c->hist_bytes -= std::min(c->hist_bytes, bytes);
+}
+/* a call's temporaries: freed when it returns, on every path */
+struct HistTemp {
+    fmgi_context *c;
+    std::vector<std::pair<void *, size_t>> v;
+    explicit HistTemp(fmgi_context *ctx) : c(ctx) {}
+    HistTemp(const HistTemp &) = delete;
+    HistTemp &operator=(const HistTemp &) = delete;
+    ~HistTemp() {
+        for (auto &q : v) hist_free(c, q.first, q.second);
+    }
+    template <class T>
+    int get(T **p, size_t bytes, const char *what) {
+        void *q = nullptr;
+        const int rc = hist_malloc(c, &q, bytes, what);
+        *p = (T *)q;
+        if (rc == FMGI_OK) v.emplace_back(q, bytes);
+        return rc;
+    }
+};
+
+static void hist_fill_info(const fmgi_context *c, fmgi_sparse_info *info) {
+    memset(info, 0, sizeof *info);
+    info->num_texels = c->num_texels;
+    info->num_blocks = fmgi_sparse_blocks(c->num_texels);
+}
+
+/* The canonical blob of the codes of src (tbits >= 0: the bake's pool, whose blocks carry tiles of 2^tbits texels
+   and are listed by tile in src.list, tile t's at [tile_first[t], tile_first[t + 1]); < 0: a plain array): bins ->
+   per batch of blocks {scatter, count, rows, scan, fill into a piece} -> the pieces joined behind the scanned
+   offsets. Synchronises s. kHistDense (nothing allocated) if a block holds 2^32 codes
+   or more: a u32 LDS counter could then wrap, and the scratch is indexed in 32 bits. */
+static int hist_build(fmgi_context *c, HistSource src, int tbits, const std::vector<uint64_t> &tile_first, hipStream_t s,
+                      unsigned long long **blob_out, fmgi_sparse_info *info, uint64_t *skipped) {
+    const int T = c->num_texels, B = fmgi_sparse_blocks(T);
+    const uint32_t halves = 2 * (uint32_t)B;
+    *blob_out = nullptr;
+    hist_fill_info(c, info);
+    if (halves > (uint32_t)kHistMaxHalves) return set_err(FMGI_ERR_STATE, "sparse bake: %d texels exceed the binning histogram", T);
+    HistTemp tmp(c);
+    src.num_texels = T;
+    const uint32_t *list = src.list; /* the bins pass reads every block in pool order */
+    const uint64_t all_segs = src.nseg;
+    src.list = nullptr;
+    src.list_lo = 0;
+    unsigned long long *d_half = nullptr; /* [halves] counts, then the skipped codes */
+    int rc = tmp.get(&d_half, ((size_t)halves + 1) * 8, "the half-block counts");
+    if (rc != FMGI_OK) return rc;
+    HIPCHK(hipMemsetAsync(d_half, 0, ((size_t)halves + 1) * 8, s));
+    HIPCHK(fmgi_launch_hist_bins(src, halves, d_half, d_half + halves, s));
+    std::vector<uint64_t> h((size_t)halves + 1);
+    HIPCHK(hipMemcpyAsync(h.data(), d_half, h.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (skipped) *skipped = h[halves];
+    uint64_t codes = 0;
+    for (int b = 0; b < B; b++) {
+        const uint64_t bc = h[2 * (size_t)b] + h[2 * (size_t)b + 1];
+        if (bc >= (1ull << 32)) return kHistDense;
+        codes += bc;
+    }
+    info->deposits = codes;
+    uint32_t *d_nz = nullptr;
+    unsigned long long *d_rows_all = nullptr;
+    rc = tmp.get(&d_nz, (size_t)B * 64 * 4, "the texels' cell counts");
+    if (rc != FMGI_OK) return rc;
+    rc = tmp.get(&d_rows_all, ((size_t)B + 1) * 8, "the blocks' row counts");
+    if (rc != FMGI_OK) return rc;
+    HIPCHK(hipMemsetAsync(d_nz, 0, (size_t)B * 64 * 4, s));
+    HIPCHK(hipMemsetAsync(d_rows_all, 0, ((size_t)B + 1) * 8, s));
+    if (!c->d_sparse_sums) HIPCHK(hipMalloc(&c->d_sparse_sums, sizeof(SparseSums)));
+    uint64_t budget = c->opt[FMGI_OPT_HIST_BATCH] > 0 ? (uint64_t)c->opt[FMGI_OPT_HIST_BATCH] : kHistBatchCodes;
+    budget = std::min<uint64_t>(budget, 1ull << 31);
+    struct Piece {
+        unsigned long long *p;
+        uint64_t rows;
+    };
+    std::vector<Piece> pieces;
+    std::vector<std::vector<uint32_t>> starts; /* the host side of every batch's upload, kept for the call */
+    /* the batches: whole blocks, at least one (a block holds fewer than 2^32 codes), at most `budget` codes; runs
+       of blocks without a code belong to no batch (d_rows_all is zero: no rows) */
+    struct Batch {
+        int b0, b1;
+        uint64_t sum;
+    };
+    std::vector<Batch> batches;
+    uint64_t scratch_cap = 0;
+    for (int b0 = 0; b0 < B;) {
+        uint64_t sum = 0;
+        int b1 = b0;
+        for (; b1 < B; b1++) {
+            const uint64_t bc = h[2 * (size_t)b1] + h[2 * (size_t)b1 + 1];
+            if (b1 > b0 && sum + bc > budget) break;
+            sum += bc;
+        }
+        if (sum) batches.push_back({b0, b1, sum});
+        scratch_cap = std::max(scratch_cap, sum);
+        b0 = b1;
+    }
+    uint32_t *d_scratch = nullptr; /* one batch's codes, sorted by half-block */
+    if (scratch_cap) {
+        rc = tmp.get(&d_scratch, (size_t)scratch_cap * 4, "a batch's codes");
+        if (rc != FMGI_OK) return rc;
+    }
+    for (const Batch &bt : batches) {
+        const int b0 = bt.b0, b1 = bt.b1;
+        const uint64_t sum = bt.sum;
+        const uint32_t nb = (uint32_t)(b1 - b0), nh = 2 * nb;
+        starts.emplace_back((size_t)nh + 1);
+        std::vector<uint32_t> &st = starts.back();
+        uint64_t run = 0;
+        for (uint32_t i = 0; i < nh; i++) {
+            st[i] = (uint32_t)run;
+            run += h[2 * (size_t)b0 + i];
+        }
+        st[nh] = (uint32_t)run; /* == sum < 2^32 */
+        uint32_t *d_start = nullptr, *d_cur = nullptr;
+        unsigned long long *d_rows = nullptr;
+        rc = tmp.get(&d_start, ((size_t)nh + 1) * 4, "a batch's run starts");
+        if (rc != FMGI_OK) return rc;
+        rc = tmp.get(&d_cur, (size_t)nh * 4, "a batch's run cursors");
+        if (rc != FMGI_OK) return rc;
+        rc = tmp.get(&d_rows, ((size_t)nb + 1) * 8, "a batch's row counts");
+        if (rc != FMGI_OK) return rc;
+        HIPCHK(hipMemcpyAsync(d_start, st.data(), ((size_t)nh + 1) * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_cur, st.data(), (size_t)nh * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(d_rows, 0, ((size_t)nb + 1) * 8, s));
+        HIPCHK(hipMemsetAsync(c->d_sparse_sums, 0, sizeof(SparseSums), s));
+        src.nseg = all_segs;
+        if (tbits >= 0 && list) { /* only the pool blocks of the batch's tiles, through the list by tile */
+            const size_t t_lo = (size_t)(((uint64_t)b0 * 64) >> tbits), t_hi = (size_t)((((uint64_t)b1 * 64 - 1) >> tbits) + 1);
+            if (t_hi >= tile_first.size()) return set_err(FMGI_ERR_STATE, "sparse bake: a batch's tiles are not in the block list");
+            src.list = list;
+            src.list_lo = tile_first[t_lo];
+            src.nseg = tile_first[t_hi] - tile_first[t_lo];
+        }
+        HIPCHK(fmgi_launch_hist_scatter(src, 2 * (uint32_t)b0, 2 * (uint32_t)b1, d_cur, d_scratch, (uint32_t)sum, s));
+        HIPCHK(fmgi_launch_hist_count(d_scratch, d_start, (uint32_t)sum, 2 * (uint32_t)b0, 2 * (uint32_t)b1, d_nz, s));
+        HIPCHK(fmgi_launch_hist_rows(d_nz, (uint32_t)b0, (uint32_t)b1, d_rows, d_rows_all, c->d_sparse_sums, s));
+        SparseSums sm;
+        HIPCHK(hipMemcpyAsync(&sm, c->d_sparse_sums, sizeof sm, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        info->rows += sm.rows;
+        info->cells += sm.cells;
+        if (sm.rows) {
+            unsigned long long *piece = nullptr;
+            rc = tmp.get(&piece, (size_t)sm.rows * 512, "a batch's rows");
+            if (rc != FMGI_OK) return rc;
+            HIPCHK(fmgi_launch_sparse_scan(d_rows, (int)nb, sm.rows, s));
+            HIPCHK(fmgi_launch_hist_fill(d_scratch, d_start, (uint32_t)sum, 2 * (uint32_t)b0, 2 * (uint32_t)b1, d_rows,
+                                         sm.rows, piece, s));
+            pieces.push_back({piece, sm.rows});
+        }
+    }
+    /* the blob: the scanned offsets, then the pieces in block order */
+    const size_t bytes = fmgi_sparse_bytes(T, info->rows);
+    void *blob = nullptr;
+    rc = hist_malloc(c, &blob, bytes, "the histogram's blob");
+    if (rc != FMGI_OK) return rc;
+    unsigned long long *w = (unsigned long long *)blob;
+    hipError_t e = hipMemcpyAsync(w, d_rows_all, ((size_t)B + 1) * 8, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = fmgi_launch_sparse_scan(w, B, info->rows, s);
+    uint64_t at = 0;
+    for (const Piece &p : pieces) {
+        if (e != hipSuccess) break;
+        e = hipMemcpyAsync(w + (size_t)B + 1 + (size_t)at * 64, p.p, (size_t)p.rows * 512, hipMemcpyDeviceToDevice, s);
+        at += p.rows;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        hist_free(c, blob, bytes);
+        return set_err(FMGI_ERR_HIP, "sparse bake: %s", hipGetErrorString(e));
+    }
+    *blob_out = w;
+    return FMGI_OK;
+}
+
+/* sum = a + b as a new blob of the sparse-bake path (measure, count, scan, fill); synchronises s */
+static int hist_add(fmgi_context *c, const unsigned long long *a, const fmgi_sparse_info &ai, const unsigned long long *b,
+                    const fmgi_sparse_info &bi, unsigned long long **sum_out, fmgi_sparse_info *si, hipStream_t s) {
+    const int T = c->num_texels;
+    if (sum_out) *sum_out = nullptr; /* (nullptr: measure only) */
+    hist_fill_info(c, si);
+    if (!c->d_sparse_sums) HIPCHK(hipMalloc(&c->d_sparse_sums, sizeof(SparseSums)));
+    HIPCHK(hipMemsetAsync(c->d_sparse_sums, 0, sizeof(SparseSums), s));
+    HIPCHK(fmgi_launch_sparse_add_count(a, ai.rows, b, bi.rows, T, nullptr, c->d_sparse_sums, s));
+    SparseSums sm;
+    HIPCHK(hipMemcpyAsync(&sm, c->d_sparse_sums, sizeof sm, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    si->rows = sm.rows;
+    si->cells = sm.cells;
+    si->deposits = sm.deposits;
+    si->too_large = sm.too_large;
+    if (sm.too_large)
+        return set_err(FMGI_ERR_ARG, "sparse sum: %llu cells reach a count of 2^%d or more", sm.too_large,
+                       FMGI_SPARSE_COUNT_BITS);
+    if (!sum_out) return FMGI_OK;
+    const size_t bytes = fmgi_sparse_bytes(T, sm.rows);
+    void *blob = nullptr;
+    const int rc = hist_malloc(c, &blob, bytes, "a sum of two blobs");
+    if (rc != FMGI_OK) return rc;
+    unsigned long long *w = (unsigned long long *)blob;
+    hipError_t e = fmgi_launch_sparse_add_count(a, ai.rows, b, bi.rows, T, w, nullptr, s);
+    if (e == hipSuccess) e = fmgi_launch_sparse_scan(w, si->num_blocks, sm.rows, s);
+    if (e == hipSuccess) e = fmgi_launch_sparse_add_fill(a, ai.rows, b, bi.rows, T, w, sm.rows, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        hist_free(c, blob, bytes);
+        return set_err(FMGI_ERR_HIP, "sparse sum: %s", hipGetErrorString(e));
+    }
+    *sum_out = w;
+    return FMGI_OK;
+}
+
+/* the histogram of one chunk joins the held one */
+static int hist_join(fmgi_context *c, unsigned long long *blob, const fmgi_sparse_info &info, hipStream_t s) {
+    if (!c->hist_held) {
+        c->hist_blob = blob;
+        c->hist_info = info;
+        c->hist_held = true;
+        return FMGI_OK;
+    }
+    unsigned long long *sum = nullptr;
+    fmgi_sparse_info si;
+    const int rc = hist_add(c, c->hist_blob, c->hist_info, blob, info, &sum, &si, s);
+    hist_free(c, blob, fmgi_sparse_bytes(c->num_texels, info.rows));
+    if (rc != FMGI_OK) return rc;
+    hist_free(c, c->hist_blob, fmgi_sparse_bytes(c->num_texels, c->hist_info.rows));
+    c->hist_blob = sum;
+    c->hist_info = si;
+    c->hist_stats.merges++;
+    return FMGI_OK;
+}
+
+/* bake_common's STREAM chunk [cb, ce) in place of its fold (fmgi_bake_sparse): the pool's codes counted into a
+   blob and joined to the held one. If the bake's bucket fallback fired, those deposits went to the scratch
+   lightmap without their state: the chunk's codes are dropped, the device stats put back to their value before
+   the chunk, and the chunk traced again with the AccState launch into a dense scratch that lives only here. */
+static int hist_chunk(fmgi_context *c, const StreamBufs &sb, uint64_t cb, uint64_t ce, hipStream_t s) {
+    const int T = c->num_texels;
+    unsigned long long now[KSTAT_ALLOC], before[KSTAT_ALLOC], cursor = 0;
+    HIPCHK(hipMemcpyAsync(now, c->d_stats, sizeof now, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(before, c->d_hist_stats, sizeof before, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&cursor, sb.cursor, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    bool dense = now[KSTAT_FALLBACK] != before[KSTAT_FALLBACK] || now[KSTAT_OVERFLOW] != before[KSTAT_OVERFLOW];
+    unsigned long long *blob = nullptr;
+    fmgi_sparse_info info;
+    if (!dense) {
+        HistSource src;
+        memset(&src, 0, sizeof src);
+        src.codes = sb.stream;
+        src.block_len = sb.block_len;
+        src.list = sb.block_list;
+        src.pool_blocks = sb.pool_blocks;
+        src.nseg = std::min<uint64_t>(cursor, sb.pool_blocks);
+        /* the pool's blocks listed by tile (the fold's own first step): tile t's at [tile_first[t], tile_first[t + 1]) */
+        uint32_t per_tile[FMGI_PRESORT_MAX_TILES + 1];
+        HIPCHK(fmgi_stream_bucket_list(sb, T, s));
+        HIPCHK(hipMemcpyAsync(per_tile, sb.tile_blocks, sizeof per_tile, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int P = (T + (1 << sb.tile_bits) - 1) >> sb.tile_bits;
+        std::vector<uint64_t> tile_first((size_t)P + 1, 0);
+        for (int t = 0; t < P; t++) tile_first[(size_t)t + 1] = tile_first[(size_t)t] + per_tile[t];
+        if (P > FMGI_PRESORT_MAX_TILES || tile_first[(size_t)P] != src.nseg)
+            return set_err(FMGI_ERR_STATE, "sparse bake: the block list holds %llu blocks, the pool %llu",
+                           (unsigned long long)tile_first[(size_t)P], (unsigned long long)src.nseg);
+        const int rc = hist_build(c, src, sb.tile_bits, tile_first, s, &blob, &info, nullptr);
+        if (rc == kHistDense) dense = true;
+        else if (rc != FMGI_OK) return rc;
+        else c->hist_stats.codes += info.deposits;
+    }
+    if (dense) {
+        HIPCHK(hipMemcpyAsync(c->d_stats, c->d_hist_stats, sizeof before, hipMemcpyDeviceToDevice, s));
+        const size_t dbytes = fmgi_states_bytes(T);
+        void *counts = nullptr;
+        int rc = hist_malloc(c, &counts, dbytes, "a chunk's dense histogram (the bucket fallback fired)");
+        if (rc != FMGI_OK) return rc;
+        auto trace = [&]() -> int {
+            HIPCHK(hipMemsetAsync(counts, 0, dbytes, s));
+            const int mode = c->accum;
+            c->accum = FMGI_ACCUM_STATE;
+            c->ext_counts = (unsigned long long *)counts;
+            c->hist_on = false;
+            const int brc = bake_common(c, cb, ce, counts, c->hist_kernel, s, false, nullptr, nullptr, nullptr);
+            c->hist_on = true;
+            c->ext_counts = nullptr;
+            c->accum = mode;
+            if (brc != FMGI_OK) return brc;
+            const int mrc = fmgi_sparse_measure(c, counts, &info, s);
+            if (mrc != FMGI_OK) return mrc;
+            void *q = nullptr;
+            const int arc = hist_malloc(c, &q, fmgi_sparse_bytes(T, info.rows), "a chunk's blob");
+            if (arc != FMGI_OK) return arc;
+            blob = (unsigned long long *)q;
+            const int crc = fmgi_sparse_compact(c, counts, &info, blob, s);
+            if (crc != FMGI_OK) return crc;
+            HIPCHK(hipStreamSynchronize(s));
+            return FMGI_OK;
+        };
+        rc = trace();
+        hist_free(c, counts, dbytes);
+        if (rc != FMGI_OK) {
+            if (blob) hist_free(c, blob, fmgi_sparse_bytes(T, info.rows));
+            return rc;
+        }
+        c->hist_stats.dense_chunks++;
+    }
+    c->hist_stats.chunks++;
+    return hist_join(c, blob, info, s);
+}
+
+FMGI_API int fmgi_bake_sparse_supported(const fmgi_context *c) {
+    if (!c) return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse_supported: null context");
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_bake_sparse_supported: no scene");
+    return stream_layout(c) == kStreamBuckets && c->num_texels < kStreamMaxTexels &&
+                   2 * fmgi_sparse_blocks(c->num_texels) <= kHistMaxHalves
+               ? 1
+               : 0;
+}
+
+static int hist_unsupported(const fmgi_context *c, const char *what) {
+    return set_err(FMGI_ERR_STATE, "%s: the scene's STREAM layout is not the per-tile bucket layout (at most %d tiles "
+                                   "of %d texels, and FMGI_OPT_STREAM_LAYOUT not 0): %d texels", what,
+                   FMGI_PRESORT_MAX_TILES, 1 << FMGI_TILE_BITS, c->num_texels);
+}
+
+/* a call of the path begins: the previous result (held, or taken and not yet freed) goes */
+static void hist_begin(fmgi_context *c) {
+    (void)hipFree(c->hist_blob);
+    c->hist_blob = nullptr;
+    c->hist_held = false;
+    memset(&c->hist_stats, 0, sizeof c->hist_stats);
+    c->hist_bytes = c->d_hist_lm ? (size_t)c->num_texels * 32 : 0;
+    c->hist_stats.scratch_bytes = c->hist_bytes;
+}
+
+/* the empty histogram as the held result */
+static int hist_hold_empty(fmgi_context *c, hipStream_t s) {
+    void *q = nullptr;
+    const size_t bytes = fmgi_sparse_bytes(c->num_texels, 0);
+    const int rc = hist_malloc(c, &q, bytes, "the empty histogram");
+    if (rc != FMGI_OK) return rc;
+    c->hist_blob = (unsigned long long *)q;
+    hist_fill_info(c, &c->hist_info);
+    c->hist_held = true;
+    HIPCHK(hipMemsetAsync(q, 0, bytes, s));
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_bake_sparse(fmgi_context *c, uint64_t item_begin, uint64_t item_end, int kernel, fmgi_sparse_info *info,
+                              void *stream) {
+    if (!c || !info) return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse: bad arguments");
+    if (item_begin > item_end)
+        return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse: item range [%llu,%llu) is reversed", (unsigned long long)item_begin,
+                       (unsigned long long)item_end);
+    if (kernel < FMGI_KERNEL_EXACT || kernel > FMGI_KERNEL_HYBRID) return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse: bad kernel %d", kernel);
+    if (c->num_texels <= 0 || c->nsrcs == 0) return set_err(FMGI_ERR_STATE, "fmgi_bake_sparse: no scene");
+    if (c->h_launches.empty() && item_end > 0) return set_err(FMGI_ERR_STATE, "fmgi_bake_sparse: no plan (fmgi_plan)");
+    if (item_end > c->total_items) /* as fmgi_bake_states reports it */
+        return set_err(FMGI_ERR_ARG, "item range [%llu,%llu) outside plan of %llu items", (unsigned long long)item_begin,
+                       (unsigned long long)item_end, (unsigned long long)c->total_items);
+    if (fmgi_bake_sparse_supported(c) != 1) return hist_unsupported(c, "fmgi_bake_sparse");
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "fmgi_bake_sparse: host-only context");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hist_begin(c);
+    if (!c->d_hist_lm) { /* the bake's lm argument: only the bucket fallback writes it, nobody reads it */
+        void *q = nullptr;
+        const int rc = hist_malloc(c, &q, (size_t)c->num_texels * 32, "the scratch lightmap");
+        if (rc != FMGI_OK) return rc;
+        c->d_hist_lm = (unsigned long long *)q;
+        HIPCHK(hipMemsetAsync(q, 0, (size_t)c->num_texels * 32, s));
+    }
+    if (!c->d_hist_stats) HIPCHK(hipMalloc(&c->d_hist_stats, KSTAT_ALLOC * sizeof(unsigned long long)));
+    int rc = ensure_colour_table(c); /* (the bucket fallback's colours) */
+    if (rc != FMGI_OK) return rc;
+    if (item_begin < item_end) {
+        const int mode = c->accum;
+        c->accum = FMGI_ACCUM_STREAM;
+        c->hist_on = true;
+        c->hist_kernel = kernel;
+        rc = bake_common(c, item_begin, item_end, c->d_hist_lm, kernel, s, false, nullptr, nullptr, nullptr);
+        c->hist_on = false;
+        c->accum = mode;
+    }
+    if (rc == FMGI_OK && !c->hist_held) rc = hist_hold_empty(c, s); /* no item, or a scene without walls */
+    if (rc == FMGI_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_err(FMGI_ERR_HIP, "fmgi_bake_sparse: synchronise failed");
+    if (rc != FMGI_OK) {
+        const std::string why = g_err;
+        hist_free(c, c->hist_blob, c->hist_held ? fmgi_sparse_bytes(c->num_texels, c->hist_info.rows) : 0);
+        c->hist_blob = nullptr;
+        c->hist_held = false;
+        g_err = why;
+        return rc;
+    }
+    *info = c->hist_info;
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_bake_sparse_take(fmgi_context *c, const fmgi_sparse_info *info, void *sparse_dev, void *stream) {
+    const int rc = sparse_call_check(c, info, sparse_dev, info, "fmgi_bake_sparse_take");
+    if (rc != FMGI_OK) return rc;
+    if (!c->hist_held) return set_err(FMGI_ERR_STATE, "fmgi_bake_sparse_take: no histogram is held");
+    if (info->rows != c->hist_info.rows)
+        return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse_take: info has %llu rows, the held histogram %llu",
+                       (unsigned long long)info->rows, (unsigned long long)c->hist_info.rows);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(hipMemcpyAsync(sparse_dev, c->hist_blob, fmgi_sparse_bytes(c->num_texels, info->rows), hipMemcpyDeviceToDevice, s));
+    c->hist_held = false; /* (its memory goes at the path's next call, fmgi_set_scene or fmgi_destroy: the copy is in flight) */
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_sparse_from_codes(fmgi_context *c, const void *codes_dev, uint64_t n, fmgi_sparse_info *info,
+                                    uint64_t *skipped, void *stream) {
+    if (!c || !codes_dev || !info || n >= (1ull << 32))
+        return set_err(FMGI_ERR_ARG, "fmgi_sparse_from_codes: bad arguments (NULL, or 2^32 codes or more)");
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "fmgi_sparse_from_codes: no scene");
+    if (fmgi_bake_sparse_supported(c) != 1) return hist_unsupported(c, "fmgi_sparse_from_codes");
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "fmgi_sparse_from_codes: host-only context");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hist_begin(c);
+    HistSource src;
+    memset(&src, 0, sizeof src);
+    src.codes = (const uint32_t *)codes_dev;
+    src.n = n;
+    src.nseg = (n + kHistSegCodes - 1) / kHistSegCodes;
+    unsigned long long *blob = nullptr;
+    fmgi_sparse_info hi;
+    const int rc = hist_build(c, src, -1, std::vector<uint64_t>(), s, &blob, &hi, skipped);
+    if (rc != FMGI_OK) /* (kHistDense: a block of 2^32 codes needs more codes than n allows) */
+        return rc == kHistDense ? set_err(FMGI_ERR_ARG, "fmgi_sparse_from_codes: too many codes") : rc;
+    c->hist_blob = blob;
+    c->hist_info = hi;
+    c->hist_held = true;
+    c->hist_stats.chunks = 1;
+    c->hist_stats.codes = hi.deposits;
+    *info = hi;
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_bake_sparse_get_stats(const fmgi_context *c, fmgi_bake_sparse_stats *out) {
+    if (!c || !out) return set_err(FMGI_ERR_ARG, "fmgi_bake_sparse_get_stats: bad arguments");
+    *out = c->hist_stats;
+    return FMGI_OK;
+}
+
+/* the checks of the two sum calls, in the documented order */
+static int sparse_add_check(const fmgi_context *c, const void *a, const fmgi_sparse_info *ai, const void *b,
+                            const fmgi_sparse_info *bi, const void *out, const fmgi_sparse_info *oi, bool out_checked,
+                            const char *what) {
+    if (!c || !a || !ai || !b || !bi || !out || !oi) return set_err(FMGI_ERR_ARG, "%s: bad arguments", what);
+    if (const char *f = sparse_info_fault(ai)) return set_err(FMGI_ERR_ARG, "%s: a: %s", what, f);
+    if (const char *f = sparse_info_fault(bi)) return set_err(FMGI_ERR_ARG, "%s: b: %s", what, f);
+    if (out_checked)
+        if (const char *f = sparse_info_fault(oi)) return set_err(FMGI_ERR_ARG, "%s: sum: %s", what, f);
+    if (c->num_texels <= 0) return set_err(FMGI_ERR_STATE, "%s: no scene", what);
+    if (ai->num_texels != c->num_texels || bi->num_texels != c->num_texels || (out_checked && oi->num_texels != c->num_texels))
+        return set_err(FMGI_ERR_ARG, "%s: an info is not of the scene's %d texels", what, c->num_texels);
+    if (c->device == FMGI_HOST_ONLY) return set_err(FMGI_ERR_NO_DEVICE, "%s: host-only context", what);
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_sparse_add_measure(fmgi_context *c, const void *a_dev, const fmgi_sparse_info *a_info, const void *b_dev,
+                                     const fmgi_sparse_info *b_info, fmgi_sparse_info *sum_info, void *stream) {
+    const int rc = sparse_add_check(c, a_dev, a_info, b_dev, b_info, sum_info, sum_info, false, "fmgi_sparse_add_measure");
+    if (rc != FMGI_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return hist_add(c, (const unsigned long long *)a_dev, *a_info, (const unsigned long long *)b_dev, *b_info, nullptr,
+                    sum_info, stream ? (hipStream_t)stream : c->stream);
+}
+
+FMGI_API int fmgi_sparse_add(fmgi_context *c, const void *a_dev, const fmgi_sparse_info *a_info, const void *b_dev,
+                             const fmgi_sparse_info *b_info, const fmgi_sparse_info *sum_info, void *sum_dev, void *stream) {
+    const int rc = sparse_add_check(c, a_dev, a_info, b_dev, b_info, sum_dev, sum_info, true, "fmgi_sparse_add");
+    if (rc != FMGI_OK) return rc;
+    if (sum_dev == a_dev || sum_dev == b_dev) return set_err(FMGI_ERR_ARG, "fmgi_sparse_add: sum_dev aliases an input");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const unsigned long long *a = (const unsigned long long *)a_dev, *b = (const unsigned long long *)b_dev;
+    unsigned long long *w = (unsigned long long *)sum_dev;
+    HIPCHK(fmgi_launch_sparse_add_count(a, a_info->rows, b, b_info->rows, c->num_texels, w, nullptr, s));
+    HIPCHK(fmgi_launch_sparse_scan(w, sum_info->num_blocks, sum_info->rows, s));
+    HIPCHK(fmgi_launch_sparse_add_fill(a, a_info->rows, b, b_info->rows, c->num_texels, w, sum_info->rows, s));
     return FMGI_OK;
 }
 

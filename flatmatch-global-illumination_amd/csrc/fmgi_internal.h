@@ -292,6 +292,8 @@ struct StreamBufs {
 };
 hipError_t fmgi_stream_fold(const StreamBufs &sb, int num_texels, unsigned long long *lm, hipStream_t s);
 int fmgi_fold_split(int tile_bits); /* fold tiles per bucket tile of 2^tile_bits texels */
+/* bucket layouts: sb.tile_blocks[0, tiles) = the tiles' block counts, sb.block_list = the pool's block ids by tile */
+hipError_t fmgi_stream_bucket_list(const StreamBufs &sb, int num_texels, hipStream_t s);
 
 #define FMGI_COLOUR_STATES 1024 /* bit 9: window (18,18,18) vs light (16,16,18); bits 0-8: 1 + diffuse-bounce floor bits */
 

@@ -22,7 +22,7 @@ from . import scene
 HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and planning only)
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
-                   SPARSE_COUNT_BITS, SparseInfo,
+                   SPARSE_COUNT_BITS, SparseInfo, BakeSparseStats,
                    VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
 from .scene import RECT_DTYPE, Scene
 
@@ -390,6 +390,60 @@ class Context:
         check(self.lib.fmgi_recolour_sparse(self.h, sp, inf, G, pal, K, lp, C.c_void_p(stream or None)),
               "fmgi_recolour_sparse")
 
+    def bake_sparse_supported(self) -> bool:
+        """fmgi_bake_sparse_supported: whether bake_sparse / sparse_from_codes can serve the current scene (its
+        STREAM layout is the per-tile bucket layout: at most 63 tiles of 2048 texels)."""
+        return bool(check(self.lib.fmgi_bake_sparse_supported(self.h), "fmgi_bake_sparse_supported"))
+
+    def bake_sparse(self, begin: int, end: int, kernel: int = KERNEL_AUTO, stream: int = 0) -> SparseInfo:
+        """fmgi_bake_sparse: bake_items' trace of work items [begin, end) through the STREAM bucket path, its deposit
+        codes counted into the sparse histogram of exactly these items (no dense histogram). The result is held in
+        the context (bake_sparse_take); returns its SparseInfo. Synchronises `stream`."""
+        info = SparseInfo()
+        check(self.lib.fmgi_bake_sparse(self.h, int(begin), int(end), int(kernel), C.byref(info),
+                                        C.c_void_p(stream or None)), "fmgi_bake_sparse")
+        return info
+
+    def bake_sparse_take(self, info: SparseInfo, sparse_ptr: int, stream: int = 0):
+        """fmgi_bake_sparse_take: the held histogram's blob (sparse_bytes(num_texels, info.rows) bytes) to sparse_ptr;
+        the context then holds nothing. Asynchronous on `stream`."""
+        check(self.lib.fmgi_bake_sparse_take(self.h, C.byref(info), C.c_void_p(sparse_ptr or None),
+                                             C.c_void_p(stream or None)), "fmgi_bake_sparse_take")
+
+    def sparse_from_codes(self, codes_ptr: int, n: int, stream: int = 0):
+        """fmgi_sparse_from_codes: the histogram of the n device codes (uint32: texel << 10 | state, any order) at
+        codes_ptr as a held result (bake_sparse_take). Returns (SparseInfo, skipped): skipped counts the codes
+        whose texel is outside the scene; codes of 0xFFFFFFFF are pads. Synchronises."""
+        info, skipped = SparseInfo(), C.c_uint64(0)
+        check(self.lib.fmgi_sparse_from_codes(self.h, C.c_void_p(codes_ptr or None), int(n), C.byref(info),
+                                              C.byref(skipped), C.c_void_p(stream or None)), "fmgi_sparse_from_codes")
+        return info, int(skipped.value)
+
+    def sparse_add_measure(self, a_ptr: int, a_info: SparseInfo, b_ptr: int, b_info: SparseInfo,
+                           stream: int = 0) -> SparseInfo:
+        """fmgi_sparse_add_measure: the SparseInfo of a + b (device blobs); synchronises. Raises FmgiError if a
+        summed count reaches 2^54."""
+        info = SparseInfo()
+        check(self.lib.fmgi_sparse_add_measure(self.h, C.c_void_p(a_ptr or None), C.byref(a_info),
+                                               C.c_void_p(b_ptr or None), C.byref(b_info), C.byref(info),
+                                               C.c_void_p(stream or None)), "fmgi_sparse_add_measure")
+        return info
+
+    def sparse_add(self, a_ptr: int, a_info: SparseInfo, b_ptr: int, b_info: SparseInfo, sum_info: SparseInfo,
+                   sum_ptr: int, stream: int = 0):
+        """fmgi_sparse_add: the canonical blob of a + b (sparse_bytes(num_texels, sum_info.rows) bytes; sum_info
+        from sparse_add_measure) to sum_ptr, which must not alias an input. Asynchronous on `stream`."""
+        check(self.lib.fmgi_sparse_add(self.h, C.c_void_p(a_ptr or None), C.byref(a_info), C.c_void_p(b_ptr or None),
+                                       C.byref(b_info), C.byref(sum_info), C.c_void_p(sum_ptr or None),
+                                       C.c_void_p(stream or None)), "fmgi_sparse_add")
+
+    def bake_sparse_stats(self) -> dict:
+        """fmgi_bake_sparse_get_stats: chunks, merges, dense_chunks, codes and scratch_bytes of the context's last
+        bake_sparse / sparse_from_codes."""
+        st = BakeSparseStats()
+        check(self.lib.fmgi_bake_sparse_get_stats(self.h, C.byref(st)), "fmgi_bake_sparse_get_stats")
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def filter_radii(self, guide_ptr: int, min_energy: int, max_radius: int, radii_ptr: int, stream: int = 0):
         """fmgi_filter_radii: per level-0 texel the smallest window radius in [0, max_radius] that holds
         min_energy (unsigned, units of 2^-25; see filter_energy) of the device guide lightmap int64
@@ -475,7 +529,7 @@ class Context:
 
     def set_option(self, name: str, value: int):
         """fmgi_set_option: one of _lib.OPTIONS (chunk_items, pool_limit, stream_layout, bucket_fill, wide_tiles,
-        coop, no_axes, photon_lock, lattice); takes effect at the next bake (no_axes: the next set_scene)."""
+        coop, no_axes, photon_lock, lattice, hist_batch); takes effect at the next bake (no_axes: the next set_scene)."""
         from ._lib import OPTIONS
 
         check(self.lib.fmgi_set_option(self.h, OPTIONS[name], int(value)), "fmgi_set_option")

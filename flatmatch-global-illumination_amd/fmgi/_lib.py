@@ -81,6 +81,13 @@ EXPORTS = (
     "fmgi_sparse_expand",
     "fmgi_recolour_sparse",
     "fmgi_sparse_check",
+    "fmgi_bake_sparse_supported",
+    "fmgi_bake_sparse",
+    "fmgi_bake_sparse_take",
+    "fmgi_sparse_from_codes",
+    "fmgi_sparse_add_measure",
+    "fmgi_sparse_add",
+    "fmgi_bake_sparse_get_stats",
     "fmgi_filter_energy",
     "fmgi_filter_radii",
     "fmgi_filter_apply",
@@ -106,7 +113,7 @@ FILTER_MAX_RADIUS = 16
 FILTER_MAX_MAPS = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
-           "no_axes": 7, "photon_lock": 8, "lattice": 9}
+           "no_axes": 7, "photon_lock": 8, "lattice": 9, "hist_batch": 10}
 
 
 class FmgiError(RuntimeError):
@@ -240,6 +247,21 @@ class SparseInfo(C.Structure):
 assert C.sizeof(SparseInfo) == 40
 
 
+class BakeSparseStats(C.Structure):
+    """fmgi_bake_sparse_stats (include/flatmatch_gi.h): the last bake_sparse / sparse_from_codes of a context."""
+
+    _fields_ = [
+        ("chunks", C.c_uint64),
+        ("merges", C.c_uint64),
+        ("dense_chunks", C.c_uint64),
+        ("codes", C.c_uint64),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(BakeSparseStats) == 40
+
+
 class Geometry(C.Structure):
     """geometry.h:7-15 (80 B)."""
 
@@ -342,6 +364,15 @@ def load() -> C.CDLL:
         "fmgi_sparse_expand": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp, vp]),
         "fmgi_recolour_sparse": (C.c_int, [vp, vp, C.POINTER(SparseInfo), C.c_int, vp, C.c_int, vp, vp]),
         "fmgi_sparse_check": (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(SparseInfo)]),
+        "fmgi_bake_sparse_supported": (C.c_int, [vp]),
+        "fmgi_bake_sparse": (C.c_int, [vp, u64, u64, C.c_int, C.POINTER(SparseInfo), vp]),
+        "fmgi_bake_sparse_take": (C.c_int, [vp, C.POINTER(SparseInfo), vp, vp]),
+        "fmgi_sparse_from_codes": (C.c_int, [vp, vp, u64, C.POINTER(SparseInfo), C.POINTER(u64), vp]),
+        "fmgi_sparse_add_measure": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp, C.POINTER(SparseInfo),
+                                              C.POINTER(SparseInfo), vp]),
+        "fmgi_sparse_add": (C.c_int, [vp, vp, C.POINTER(SparseInfo), vp, C.POINTER(SparseInfo),
+                                      C.POINTER(SparseInfo), vp, vp]),
+        "fmgi_bake_sparse_get_stats": (C.c_int, [vp, C.POINTER(BakeSparseStats)]),
         "fmgi_filter_energy": (u64, [C.POINTER(Palette), u64]),
         "fmgi_filter_radii": (C.c_int, [vp, vp, u64, C.c_int, vp, vp]),
         "fmgi_filter_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),

@@ -399,6 +399,53 @@ int fmgi_recolour_sparse(fmgi_context *ctx, const void *const *sparse_dev, const
    fmgi_last_error naming the first violation. info->too_large is 0 (a count field cannot hold more). */
 int fmgi_sparse_check(const void *sparse_host, size_t bytes, int num_texels, fmgi_sparse_info *info);
 
+/* ---- Sparse histograms from the bake's deposit codes, and the sum of two blobs ------- */
+/* A deposit code of the STREAM bake is texel << 10 | state: the key of a sparse cell. The calls below count codes
+   into a sparse histogram without ever holding the dense uint64 [1024][T] form, and add two blobs cell by cell.
+   Argument checks run on the host before any device call, in the order of the sparse calls above: FMGI_ERR_ARG
+   (NULL context or pointer, an info with a wrong num_blocks or too_large != 0, item_begin > item_end);
+   FMGI_ERR_STATE (no scene; for the bake also no plan), then for the bake a range past the plan as
+   fmgi_bake_states reports it (FMGI_ERR_ARG); FMGI_ERR_ARG (an info whose
+   num_texels is not the scene's); FMGI_ERR_STATE where fmgi_bake_sparse_supported is 0 (the two calls that count
+   codes); FMGI_ERR_NO_DEVICE on a host-only context. fmgi_set_scene and fmgi_destroy release a held result. */
+/* 1 if fmgi_bake_sparse / fmgi_sparse_from_codes can serve the current scene (its STREAM layout is the per-tile
+   bucket layout: at most 63 tiles of 2048 texels, and FMGI_OPT_STREAM_LAYOUT does not force the sliced layout),
+   0 if not, FMGI_ERR_ARG / FMGI_ERR_STATE for a NULL context / no scene. Host only. */
+int fmgi_bake_sparse_supported(const fmgi_context *ctx);
+/* fmgi_bake_items' trace of work items [item_begin, item_end) through the STREAM bucket path, whatever
+   fmgi_set_accumulation selected (left as it is), with the deposit codes counted into the sparse histogram of
+   exactly these items. The result is held in the context, replacing one held before; *info describes it.
+   Synchronises `stream`. item_begin == item_end gives the empty histogram (rows 0). A chunk of the bake whose
+   bucket fallback fired (fmgi_stats.bucket_fallback_codes moved: those deposits went to a lightmap and lost
+   their state), or that holds 2^32 codes or more of one 32-texel half-block, is traced again through
+   fmgi_bake_states' route into a dense scratch that lives for that chunk only (FMGI_ERR_OOM, nothing held, if it
+   cannot be allocated); the result and the context's fmgi_stats are the same either way. */
+int fmgi_bake_sparse(fmgi_context *ctx, uint64_t item_begin, uint64_t item_end, int kernel,
+                     fmgi_sparse_info *info, void *stream);
+/* Writes the held histogram's canonical blob, fmgi_sparse_bytes(T, info->rows) bytes, to sparse_dev and releases
+   it. FMGI_ERR_STATE if nothing is held; FMGI_ERR_ARG if info->rows / num_texels are not the held ones. Async. */
+int fmgi_bake_sparse_take(fmgi_context *ctx, const fmgi_sparse_info *info, void *sparse_dev, void *stream);
+/* The histogram of n device codes (texel << 10 | state, any order) as a held result like fmgi_bake_sparse's. A code
+   equal to 0xFFFFFFFF, or whose texel is >= numTexels, is skipped; *skipped (may be NULL) receives how many of the
+   latter. n < 2^32. Synchronises. */
+int fmgi_sparse_from_codes(fmgi_context *ctx, const void *codes_dev, uint64_t n, fmgi_sparse_info *info,
+                           uint64_t *skipped, void *stream);
+/* sum = a + b, cell by cell (counts add; a cell of either is a cell of the sum), in canonical form.
+   _measure synchronises and fills *sum_info (FMGI_ERR_ARG with the info filled if a summed count reaches 2^54);
+   fmgi_sparse_add writes fmgi_sparse_bytes(T, sum_info->rows) bytes, asynchronous, offsets recomputed and
+   clamped to sum_info->rows as fmgi_sparse_compact does. sum_dev must not alias a_dev or b_dev. */
+int fmgi_sparse_add_measure(fmgi_context *ctx, const void *a_dev, const fmgi_sparse_info *a_info, const void *b_dev,
+                            const fmgi_sparse_info *b_info, fmgi_sparse_info *sum_info, void *stream);
+int fmgi_sparse_add(fmgi_context *ctx, const void *a_dev, const fmgi_sparse_info *a_info, const void *b_dev,
+                    const fmgi_sparse_info *b_info, const fmgi_sparse_info *sum_info, void *sum_dev, void *stream);
+typedef struct fmgi_bake_sparse_stats {  /* of the last fmgi_bake_sparse / fmgi_sparse_from_codes of the context */
+    uint64_t chunks, merges;             /* bake chunks counted; blob sums that joined them                      */
+    uint64_t dense_chunks;               /* chunks that took the dense fallback (above); 0 on a healthy run      */
+    uint64_t codes;                      /* codes counted from the pool (== info.deposits when dense_chunks == 0) */
+    uint64_t scratch_bytes;              /* device bytes this path held at its peak, the stream pool excluded    */
+} fmgi_bake_sparse_stats;
+int fmgi_bake_sparse_get_stats(const fmgi_context *ctx, fmgi_bake_sparse_stats *out);
+
 /* ---- Adaptive density filter for noisy, low-photon lightmaps ------------------------ */
 /* A radiance estimate on the binned photons: per level-0 texel a square window, grown until it holds enough
    deposit energy and clipped to the texel's own wall, then the mean over that window. No reference counterpart.
@@ -495,7 +542,9 @@ int fmgi_experiments(void);
      FMGI_OPT_LATTICE       0 / 1: the staged and compact closed boxes whose six planes are verified lattices of
                             rects (fmgi_lattice_copy) through their grid cells / the lattice cell of the nearest
                             plane; -1: by the configuration (any other value: FMGI_ERR_ARG). A scene without a
-                            lattice runs its ordinary instance whatever the value. */
+                            lattice runs its ordinary instance whatever the value.
+     FMGI_OPT_HIST_BATCH    > 0: at most this many codes per counting batch of fmgi_bake_sparse and
+                            fmgi_sparse_from_codes (several batches per chunk); 0: 64 Mi codes */
 #define FMGI_OPT_CHUNK_ITEMS 1
 #define FMGI_OPT_POOL_LIMIT 2
 #define FMGI_OPT_STREAM_LAYOUT 3
@@ -505,7 +554,8 @@ int fmgi_experiments(void);
 #define FMGI_OPT_NO_AXES 7
 #define FMGI_OPT_PHOTON_LOCK 8
 #define FMGI_OPT_LATTICE 9
-#define FMGI_OPT_COUNT 10
+#define FMGI_OPT_HIST_BATCH 10
+#define FMGI_OPT_COUNT 11
 int fmgi_set_option(fmgi_context *ctx, int option, int64_t value);
 /* Profiling builds only (make timing -> libflatmatch_gi_timing.so, -DFMGI_STAGE_TIMING): shader-clock
    cycles summed over waves per bake-loop stage {start, sample, scan phase 1, phase 2, fallback, hit,

@@ -31,7 +31,10 @@ traced, through one reused dense scratch histogram, and the scenarios are folded
 per group, the same lightmaps bit for bit. --save-bake FILE (implies --sparse) writes the traced scene to one .npz
 (fmgi.save_bake); --load-bake FILE lights it again without tracing anything: --spa is then optional (it is taken
 from the file and must agree if given) and --per-light follows the file's groups. A file baked for another scene is
-refused before any device is touched.
+refused before any device is touched. --sparse-from-codes (implies --sparse) traces every group with
+fmgi.Context.bake_sparse: the bake's deposit codes are counted straight into the blob, so no dense
+histogram exists at any time; the blobs, the outputs and a saved bake file are the same bytes. A scene the call
+cannot serve (more than 63 tiles of 2048 texels) takes the --sparse route, and the run says so.
 
   python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --scenarios scenarios.json -o out
   python tools/relight.py tests/golden/example_geometry.bin --spa 6500000 --per-light --save-bake example.npz --scenarios a.json
@@ -139,7 +142,14 @@ def parse_args(argv=None):
                     help="compact every group's histogram into its sparse form and recolour from the blobs")
     ap.add_argument("--save-bake", default=None, metavar="FILE", help="write the traced scene to FILE (implies --sparse)")
     ap.add_argument("--load-bake", default=None, metavar="FILE", help="light the bake of FILE: nothing is traced")
+    ap.add_argument("--sparse-from-codes", action="store_true",
+                    help="trace every group with bake_sparse: the blobs from the deposit codes, no dense scratch "
+                         "histogram (implies --sparse)")
     a = ap.parse_args(argv)
+    if a.sparse_from_codes and a.load_bake is not None:
+        ap.error("--sparse-from-codes with --load-bake: nothing is traced")
+    if a.sparse_from_codes:
+        a.sparse = True
     if a.load_bake is None and a.spa is None:
         ap.error("the following arguments are required: --spa")
     if a.load_bake is not None and a.save_bake is not None:
@@ -191,12 +201,26 @@ def main(argv=None):
     kernel = {"auto": fmgi.KERNEL_AUTO, "exact": fmgi.KERNEL_EXACT, "fast": fmgi.KERNEL_FAST,
               "grid": fmgi.KERNEL_GRID, "hybrid": fmgi.KERNEL_HYBRID}[a.kernel]
     T = sc.num_texels
+    from_codes = []  # --sparse-from-codes: per group (dense_chunks, scratch_bytes)
     s = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(s):
         if loaded is not None:
             infos = [g["info"] for g in loaded["groups"]]
             blobs = [torch.from_numpy(g["blob"].view(np.int64)).to(dev) for g in loaded["groups"]]
+        elif a.sparse_from_codes and ctx.bake_sparse_supported():
+            infos, blobs = [], []
+            for _, b, e, _ in groups:
+                info = ctx.bake_sparse(b, e, kernel, s.cuda_stream)
+                blob = torch.empty(fmgi.sparse_bytes(T, info.rows) // 8, dtype=torch.int64, device=dev)
+                ctx.bake_sparse_take(info, blob.data_ptr(), s.cuda_stream)
+                infos.append(info)
+                blobs.append(blob)
+                st = ctx.bake_sparse_stats()
+                from_codes.append((st["dense_chunks"], st["scratch_bytes"]))
         elif a.sparse:
+            if a.sparse_from_codes:
+                print(f"{sc.name}: --sparse-from-codes cannot serve {T} texels (more than 63 tiles of 2048): "
+                      "the --sparse route through one dense scratch histogram instead")
             # one dense scratch histogram for every group in turn: bake, measure, compact, zero
             scratch = torch.zeros((fmgi.COLOUR_STATE_COUNT, T), dtype=torch.int64, device=dev)
             infos, blobs = [], []
@@ -250,6 +274,9 @@ def main(argv=None):
               f"{', '.join(f'{g[0]} {n / 2**20:.2f} MiB' for g, n in zip(groups, sizes))} "
               f"({100.0 * sum(sizes) / (len(groups) * fmgi.states_bytes(T)):.1f} % of dense, fill "
               f"{cells / max(slots, 1):.2f}), {len(entries)} scenarios")
+        if from_codes:
+            print(f"  from the deposit codes: peak scratch {max(v[1] for v in from_codes) / 2**20:.2f} MiB (a dense "
+                  f"histogram: {fmgi.states_bytes(T) / 2**20:.1f} MiB), {sum(v[0] for v in from_codes)} dense chunks")
         if a.save_bake is not None:
             print(f"  bake saved to {a.save_bake}: {os.path.getsize(a.save_bake)} bytes")
     if a.min_deposits > 0:
