@@ -295,6 +295,28 @@ done:
 
 } // namespace
 
+OutWallIn fmgi_out_wall_in(const fmgi_rect &r, int64_t first_tile) {
+    OutWallIn in;
+    in.first_tile = first_tile;
+    in.s0 = r.lightmapSetup[0];
+    in.floor = r.pos.s[2] == 0 && r.width.s[2] == 0 && r.height.s[2] == 0;
+    in.nt = r.lightmapSetup[1] * r.lightmapSetup[2];
+    in.area = length(f3of(r.width)) * length(f3of(r.height));
+    return in;
+}
+
+OutWall fmgi_out_wall(const OutWallIn &in, int spa) {
+    OutWall w;
+    memset(&w, 0, sizeof w);
+    w.first_tile = in.first_tile;
+    w.s0 = in.s0;
+    w.floor = in.floor;
+    /* main.c:71: getNumTiles(obj) / (getArea(obj) * numSamplesPerArea), then 0.35 * that in double */
+    const float per = in.nt / (in.area * spa);
+    w.norm = (float)(0.35 * per);
+    return w;
+}
+
 namespace {
 
 int output_run(const fmgi_geometry *geo, int spa, int tint, fmgi_vec3 *texels_out, uint8_t *rgb_out) {
@@ -309,17 +331,9 @@ int output_run(const fmgi_geometry *geo, int spa, int tint, fmgi_vec3 *texels_ou
         const int32_t *lm = r.lightmapSetup;
         if (lm[1] < 1 || lm[2] < 1 || lm[0] < 0 || (int64_t)lm[0] + (int64_t)lm[1] * lm[2] > geo->numTexels)
             return internal_set_err(FMGI_ERR_ARG, "fmgi_output_tiles: a wall's texels lie outside numTexels");
-        OutWall &w = ow[i];
-        memset(&w, 0, sizeof w);
-        w.first_tile = tiles;
-        w.s0 = lm[0];
-        w.floor = r.pos.s[2] == 0 && r.width.s[2] == 0 && r.height.s[2] == 0;
-        const int nt = lm[1] * lm[2];
-        /* main.c:71: getNumTiles(obj) / (getArea(obj) * numSamplesPerArea), then 0.35 * that in double */
-        const float area = length(f3of(r.width)) * length(f3of(r.height));
-        const float per = nt / (area * spa);
-        w.norm = (float)(0.35 * per);
-        tiles += nt;
+        const OutWallIn in = fmgi_out_wall_in(r, tiles);
+        ow[i] = fmgi_out_wall(in, spa);
+        tiles += in.nt;
     }
     if (texels_out != geo->texels) memcpy(texels_out, geo->texels, (size_t)geo->numTexels * sizeof(fmgi_vec3));
     if (tiles == 0) return FMGI_OK;

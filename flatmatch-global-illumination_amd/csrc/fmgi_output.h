@@ -22,8 +22,21 @@ struct OutArgs {
     float *texels;   /* float4 per texel, normalised in place when `normalise` */
     uint8_t *rgb;    /* 3 B per level-0 texel */
     int normalise, tint_extra;
+    const float *texels_in; /* fmgi_launch_output_const: float4 per texel, read only (texels unused) */
 };
 
 hipError_t fmgi_launch_output(const OutArgs &a, hipStream_t s);
+/* the same tiles from texels_in, which stay as they are */
+hipError_t fmgi_launch_output_const(const OutArgs &a, hipStream_t s);
+
+/* what a wall's OutWall is made of, apart from numSamplesPerArea (fmgi_ao_host.cpp) */
+struct OutWallIn {
+    int64_t first_tile;
+    int32_t s0, floor, nt; /* nt: level-0 tiles */
+    float area;            /* getArea: |width| * |height| */
+};
+struct fmgi_rect;
+OutWallIn fmgi_out_wall_in(const fmgi_rect &r, int64_t first_tile);
+OutWall fmgi_out_wall(const OutWallIn &in, int spa);
 
 #endif

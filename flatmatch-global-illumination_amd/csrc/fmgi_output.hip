@@ -23,6 +23,9 @@ __device__ __forceinline__ uint8_t to_byte(float d) { /* clamp() rectangle.c:288
     return (uint8_t)(int)d;
 }
 
+/* IN_PLACE: the texels are normalised where they lie (fmgi_output_tiles); otherwise they are read from
+   texels_in and nothing but the tiles is written (fmgi_view_cache_tiles) */
+template <bool IN_PLACE>
 __global__ __launch_bounds__(256) void k_output(OutArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.ntexels) return;
@@ -33,11 +36,17 @@ __global__ __launch_bounds__(256) void k_output(OutArgs a) {
     }
     const OutWall w = a.walls[lo];
     const int64_t j = i - w.first_tile;
-    float4 *t = (float4 *)a.texels + w.s0 + j;
-    float4 c = *t;
-    if (a.normalise) {
-        c = make_float4(c.x * w.norm, c.y * w.norm, c.z * w.norm, 0.0f);
-        *t = c;
+    float4 c;
+    if constexpr (IN_PLACE) {
+        float4 *t = (float4 *)a.texels + w.s0 + j;
+        c = *t;
+        if (a.normalise) {
+            c = make_float4(c.x * w.norm, c.y * w.norm, c.z * w.norm, 0.0f);
+            *t = c;
+        }
+    } else {
+        c = ((const float4 *)a.texels_in)[w.s0 + j];
+        if (a.normalise) c = make_float4(c.x * w.norm, c.y * w.norm, c.z * w.norm, 0.0f);
     }
     const float lum = (float)(0.2126 * (double)c.x + 0.7152 * (double)c.y + 0.0722 * (double)c.z);
     const float per = (float)(1 - exp((double)(-2 * lum)));
@@ -62,6 +71,13 @@ __global__ __launch_bounds__(256) void k_output(OutArgs a) {
 
 hipError_t fmgi_launch_output(const OutArgs &a, hipStream_t s) {
     if (a.ntexels <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_output, dim3((unsigned)((a.ntexels + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_output<true>, dim3((unsigned)((a.ntexels + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_launch_output_const(const OutArgs &a, hipStream_t s) {
+    if (a.ntexels <= 0) return hipSuccess;
+    if (!a.texels_in || !a.rgb || !a.walls || a.nwalls < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_output<false>, dim3((unsigned)((a.ntexels + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -79,6 +79,39 @@ struct ShadeArgs {
     int x0, y0, x1, y1;    /* this launch's pixels */
 };
 
+/*
+ * The traced view (fmgi_view_cache_*): k_view_trace casts k_view_shade's rays once and keeps every
+ * sample's taps, k_view_resolve shades any number of tile sets from them.
+ * Records are sample-major: sample n = j * S + i of camera c, pixel (y, x), lives at [c][n][y][x].
+ *   NEAREST   one uint32: first_tile[wall] + ty * s1 + tx, or FMGI_VIEW_MISS
+ *   BILINEAR  16 B {uint32 t00, uint32 t10, float fu, float fv}:
+ *             t00 = (first_tile + ya * s1 + xa) | (xb != xa) << 31, t10 = first_tile + yb * s1 + xa, fu and fv
+ *             tap_axis's weights; a miss is t00 = FMGI_VIEW_MISS
+ * so a scene of a traced view holds fewer than 2^31 tiles.
+ */
+#define FMGI_VIEW_SETS 8 /* tile sets per k_view_resolve pass: FMGI_VIEW_CACHE_MAX_SETS of the C ABI */
+#define FMGI_VIEW_MISS 0xFFFFFFFFu
+
+struct TraceArgs {
+    ShadeArgs s;               /* as k_view_shade reads it; tiles, cov_out, rgb_out and background unused */
+    void *records;             /* [ncams][samples^2][height][width] records of this launch's cameras */
+    unsigned long long *hits;  /* one counter: rays that hit a wall */
+};
+
+struct ResolveArgs {
+    const void *records;                  /* [ncams][samples^2][height][width] */
+    const uint32_t *tiles[FMGI_VIEW_SETS]; /* per set: one word per tile, as k_view_pack makes them */
+    uint8_t *rgb[FMGI_VIEW_SETS];          /* per set: [ncams][height][width][3] */
+    uint8_t *cov_out;                     /* [ncams][height][width], or null */
+    int nsets;                            /* 1 .. FMGI_VIEW_SETS */
+    int ncams, width, height;
+    int samples, filter;
+    uint32_t background; /* r | g << 8 | b << 16 */
+};
+
+hipError_t fmgi_view_launch_trace(const TraceArgs &t, hipStream_t s);
+hipError_t fmgi_view_launch_resolve(const ResolveArgs &r, hipStream_t s);
+
 hipError_t fmgi_view_launch_candidates(const ViewArgs &a, hipStream_t s);
 hipError_t fmgi_view_launch_rays(const ViewArgs &a, hipStream_t s);
 /* RGB8 tiles -> one word per tile */

@@ -249,6 +249,142 @@ __global__ __launch_bounds__(256) void k_view_shade(ShadeArgs s) {
     if (lane == 0 && n) atomicAdd(a.tests, n);
 }
 
+/* sample n of camera c, pixel (y, x): its record's index in [c][n][y][x] */
+__device__ __forceinline__ int64_t record_index(int c, int spp, int n, int height, int width, int y, int x) {
+    return (((int64_t)c * spp + n) * height + y) * width + x;
+}
+
+/*
+ * k_view_shade's rays without its colours (fmgi_view_cache_create): the same pixel mapping, sample loop and
+ * walk, so the candidate index stays wave-uniform; every sample's taps go to its record (fmgi_view.h) and
+ * nothing is shaded. tests and hits are counted per lane, one atomic per wave each.
+ */
+__global__ __launch_bounds__(256) void k_view_trace(TraceArgs t) {
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    unsigned long long tests = 0, hits = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool bilinear = s.filter != 0;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        for (int j = 0; j < S; j++) {
+            const float fy = -V.pixel * (py + s.offs[j]);
+            for (int i = 0; i < S; i++) {
+                const float fx = V.pixel * (px + s.offs[i]);
+                const v3 dir = view_dir(V, cam, fx, fy);
+                float dist;
+                const int target = view_walk(a, keys, C, cam, dir, dist, tests);
+                const int64_t o = record_index(c, S * S, j * S + i, a.height, a.width, y, x);
+                uint4 rec = make_uint4(FMGI_VIEW_MISS, 0u, 0u, 0u);
+                if (target >= 0) {
+                    hits++;
+                    const RadRect tr = a.rects[target];
+                    float u, v;
+                    view_uv(a.hits[target], tr, cam, dir, dist, u, v);
+                    const uint32_t first = (uint32_t)a.first_tile[target];
+                    if (!bilinear) {
+                        rec.x = first + (uint32_t)(clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1));
+                    } else {
+                        int xa, xb, ya, yb;
+                        float fu, fv;
+                        tap_axis(u, tr.s1, xa, xb, fu);
+                        tap_axis(v, tr.s2, ya, yb, fv);
+                        rec.x = (first + (uint32_t)(ya * tr.s1 + xa)) | ((uint32_t)(xb != xa) << 31);
+                        rec.y = first + (uint32_t)(yb * tr.s1 + xa);
+                        rec.z = __float_as_uint(fu);
+                        rec.w = __float_as_uint(fv);
+                    }
+                }
+                if (bilinear) ((uint4 *)t.records)[o] = rec;
+                else ((uint32_t *)t.records)[o] = rec.x;
+            }
+        }
+    }
+    const unsigned long long n = wave_sum(tests), h = wave_sum(hits);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
+    if (lane == 0 && h) atomicAdd(t.hits, h);
+}
+
+/*
+ * The gather (fmgi_view_cache_shade): one lane per pixel, k_view_shade's pixel mapping over the whole image. Per
+ * sample the record is read once and every tile set of the pass gathers its tap words (4 B each, served by L2)
+ * and adds k_view_shade's fixed-point colour to its own integer sums. The loop over the sets is unrolled with a
+ * uniform guard, so the sums stay in registers.
+ */
+template <bool BILINEAR>
+__global__ __launch_bounds__(256) void k_view_resolve(ResolveArgs r) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    if (x >= r.width || y >= r.height) return;
+    const int spp = r.samples * r.samples;
+    const int bg0 = fix8((float)(r.background & 255)), bg1 = fix8((float)((r.background >> 8) & 255)),
+              bg2 = fix8((float)((r.background >> 16) & 255));
+    int sum0[FMGI_VIEW_SETS], sum1[FMGI_VIEW_SETS], sum2[FMGI_VIEW_SETS], cov = 0;
+#pragma unroll
+    for (int k = 0; k < FMGI_VIEW_SETS; k++) sum0[k] = sum1[k] = sum2[k] = 0;
+    for (int n = 0; n < spp; n++) {
+        const int64_t o = record_index(c, spp, n, r.height, r.width, y, x);
+        if constexpr (BILINEAR) {
+            /* a native vector, so that the record stays one 16-byte load */
+            typedef uint32_t rec4 __attribute__((ext_vector_type(4)));
+            const rec4 rec = ((const rec4 *)r.records)[o];
+            const bool hit = rec.x != FMGI_VIEW_MISS;
+            cov += hit;
+            const uint32_t t00 = rec.x & 0x7FFFFFFFu, dx = rec.x >> 31, t10 = rec.y;
+            const float fu = __uint_as_float(rec.z), fv = __uint_as_float(rec.w);
+#pragma unroll
+            for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+                if (k >= r.nsets) break;
+                if (!hit) {
+                    sum0[k] += bg0, sum1[k] += bg1, sum2[k] += bg2;
+                    continue;
+                }
+                const uint32_t *T = r.tiles[k];
+                const uint32_t w00 = T[t00], w01 = T[t00 + dx], w10 = T[t10], w11 = T[t10 + dx];
+#define FMGI_CH(sh)                                                                                        \
+    fix8(lerp2(fv, lerp2(fu, (float)((w00 >> sh) & 255), (float)((w01 >> sh) & 255)),                    \
+               lerp2(fu, (float)((w10 >> sh) & 255), (float)((w11 >> sh) & 255))))
+                sum0[k] += FMGI_CH(0), sum1[k] += FMGI_CH(8), sum2[k] += FMGI_CH(16);
+#undef FMGI_CH
+            }
+        } else {
+            const uint32_t rec = ((const uint32_t *)r.records)[o];
+            const bool hit = rec != FMGI_VIEW_MISS;
+            cov += hit;
+#pragma unroll
+            for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+                if (k >= r.nsets) break;
+                if (!hit) {
+                    sum0[k] += bg0, sum1[k] += bg1, sum2[k] += bg2;
+                    continue;
+                }
+                const uint32_t w = r.tiles[k][rec];
+                sum0[k] += fix8((float)(w & 255)), sum1[k] += fix8((float)((w >> 8) & 255)), sum2[k] += fix8((float)((w >> 16) & 255));
+            }
+        }
+    }
+    const int64_t o = ((int64_t)c * r.height + y) * r.width + x;
+    const int half = 128 * spp, den = 256 * spp;
+#pragma unroll
+    for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+        if (k >= r.nsets) break;
+        uint8_t *q = r.rgb[k] + 3 * o;
+        q[0] = (uint8_t)((sum0[k] + half) / den);
+        q[1] = (uint8_t)((sum1[k] + half) / den);
+        q[2] = (uint8_t)((sum2[k] + half) / den);
+    }
+    if (r.cov_out) r.cov_out[o] = (uint8_t)cov;
+}
+
 bool bad_sort(const ViewArgs &a) {
     return a.sort_n < 2 || a.sort_n > FMGI_RAD_MAX_SORT || (a.sort_n & (a.sort_n - 1)) || a.nrects > a.sort_n;
 }
@@ -294,5 +430,35 @@ hipError_t fmgi_view_launch_shade(const ShadeArgs &s, hipStream_t st) {
     const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
                     (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
     hipLaunchKernelGGL(k_view_shade, grid, dim3(256), 0, st, s);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_trace(const TraceArgs &t, hipStream_t st) {
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a) || a.ncams > FMGI_VIEW_MAX_BATCH || a.width < 1 || a.height < 1 ||
+        a.width > FMGI_VIEW_MAX_DIM || a.height > FMGI_VIEW_MAX_DIM || !a.first_tile || !t.records || !t.hits ||
+        s.samples < 1 || s.samples > FMGI_VIEW_SAMPLES || (s.filter != 0 && s.filter != 1) || s.x0 < 0 || s.y0 < 0 ||
+        s.x1 <= s.x0 || s.y1 <= s.y0 || s.x1 > a.width || s.y1 > a.height)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    hipLaunchKernelGGL(k_view_trace, grid, dim3(256), 0, st, t);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_resolve(const ResolveArgs &r, hipStream_t st) {
+    if (r.ncams <= 0) return hipSuccess;
+    if (r.ncams > FMGI_VIEW_MAX_BATCH || r.width < 1 || r.height < 1 || r.width > FMGI_VIEW_MAX_DIM ||
+        r.height > FMGI_VIEW_MAX_DIM || r.samples < 1 || r.samples > FMGI_VIEW_SAMPLES ||
+        (r.filter != 0 && r.filter != 1) || !r.records || r.nsets < 1 || r.nsets > FMGI_VIEW_SETS)
+        return hipErrorInvalidValue;
+    for (int k = 0; k < r.nsets; k++)
+        if (!r.tiles[k] || !r.rgb[k]) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((r.width + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((r.height + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)r.ncams);
+    if (r.filter) hipLaunchKernelGGL(k_view_resolve<true>, grid, dim3(256), 0, st, r);
+    else hipLaunchKernelGGL(k_view_resolve<false>, grid, dim3(256), 0, st, r);
     return hipGetLastError();
 }

@@ -8,7 +8,9 @@
  * reference's order (built with -ffp-contract=off, no FMA), uploads the walls as the radiosity backend's
  * RadRect / AoRect images, runs the two kernels (fmgi_view.hip) over chunks of cameras and copies the
  * requested outputs back. fmgi_shade_views (supersampled, filtered views; no reference program) takes the same
- * path into k_view_shade, in launches of a bounded number of rays.
+ * path into k_view_shade, in launches of a bounded number of rays. fmgi_view_cache_* (traced views)
+ * casts the same rays once with k_view_trace and shades device-resident lightmaps with k_output's read-only form
+ * and k_view_resolve, asynchronously on the caller's stream.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "../../include/flatmatch_gi.h"
+#include "fmgi_output.h"
 #include "fmgi_view.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
@@ -438,6 +441,294 @@ done:
 }
 
 } // namespace
+
+/*
+ * The traced view: fmgi_view_cache_create casts a view's rays once into per-sample records,
+ * fmgi_view_cache_tiles runs the output step on device lightmaps and fmgi_view_cache_shade gathers the pictures.
+ * The handle owns the records, the output step's wall table and the packed-tile scratch of a pass.
+ */
+struct fmgi_view_cache {
+    int device = 0;
+    struct fmgi_view_cache_info info;
+    std::vector<OutWallIn> walls; /* what the OutWall table is made of; norm follows the call's spa */
+    DevBuf records, out_walls, packed;
+    int out_spa = -1;        /* the spa out_walls holds, -1: none yet */
+    int packed_sets = 0;     /* sets `packed` has room for */
+    hipEvent_t ev_tiles = nullptr, ev_shade = nullptr; /* the last launch that reads out_walls / packed */
+    bool tiles_pending = false, shade_pending = false;
+    ~fmgi_view_cache() {
+        if (ev_tiles) hipEventDestroy(ev_tiles);
+        if (ev_shade) hipEventDestroy(ev_shade);
+    }
+};
+
+static_assert(FMGI_VIEW_SETS == FMGI_VIEW_CACHE_MAX_SETS, "kernel and ABI set limits differ");
+
+namespace {
+
+/* the argument checks fmgi_view_cache_bytes and fmgi_view_cache_create share; nullptr: fine */
+const char *cache_shape_error(int num_cams, bool have_cams, int width, int height, int samples, int filter) {
+    if (width < 1 || height < 1 || width > FMGI_VIEW_MAX_DIM || height > FMGI_VIEW_MAX_DIM) return "bad image size";
+    if (num_cams < 1 || num_cams > FMGI_VIEW_MAX_BATCH || !have_cams) return "bad cameras";
+    if (samples < 1 || samples > FMGI_VIEW_MAX_SAMPLES) return "samples outside 1..8";
+    if (filter != FMGI_VIEW_NEAREST && filter != FMGI_VIEW_BILINEAR) return "filter is neither nearest nor bilinear";
+    return nullptr;
+}
+
+int64_t cache_bytes(int num_cams, int width, int height, int samples, int filter) {
+    return (int64_t)num_cams * width * height * samples * samples * (filter == FMGI_VIEW_BILINEAR ? 16 : 4);
+}
+
+int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height, int samples,
+                 int filter, fmgi_view_cache **out) {
+    static const char fn[] = "fmgi_view_cache_create";
+    if (!out) return arg_err(fn, "null out");
+    *out = nullptr;
+    Walls w;
+    int rc = check_geometry(geo, w, fn);
+    if (rc != FMGI_OK) return rc;
+    if (const char *msg = cache_shape_error(num_cams, cams != nullptr, width, height, samples, filter))
+        return arg_err(fn, msg);
+    std::vector<ViewCam> vc((size_t)num_cams);
+    for (int i = 0; i < num_cams; i++)
+        if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
+    const int nr = geo->numWalls;
+    std::vector<OutWallIn> ow((size_t)nr);
+    int64_t ntiles = 0;
+    for (int i = 0; i < nr; i++) {
+        ow[(size_t)i] = fmgi_out_wall_in(geo->walls[i], ntiles);
+        ntiles += ow[(size_t)i].nt;
+    }
+    if (ntiles >= ((int64_t)1 << 31)) return arg_err(fn, "2^31 tiles or more: a record holds a tile in 31 bits");
+    if ((rc = no_device()) != FMGI_OK) return rc;
+
+    const int64_t pix = (int64_t)width * height, spp = (int64_t)samples * samples, budget = shade_ray_budget();
+    const size_t rec = filter == FMGI_VIEW_BILINEAR ? 16 : 4;
+    /* cameras per launch and one camera's windows: as shade_run sizes them */
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)num_cams, budget / (pix * spp)));
+    int rows = height, cols = width;
+    if (pix * spp > budget) {
+        const int64_t B = FMGI_VIEW_BLOCK;
+        rows = (int)std::min<int64_t>(height, std::max<int64_t>(B, budget / ((int64_t)width * spp) / B * B));
+        cols = (int)std::min<int64_t>(width, std::max<int64_t>(B, budget / ((int64_t)rows * spp) / B * B));
+    }
+    fmgi_view_cache *v = new fmgi_view_cache;
+    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_counters, d_first;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    unsigned long long counters[2] = {0, 0};
+    float ms = 0;
+    TraceArgs t;
+    memset(&t, 0, sizeof t);
+    ShadeArgs &s = t.s;
+    ViewArgs &a = s.v;
+    {
+        const char *dv = getenv("FMGI_DEVICE");
+        v->device = dv ? atoi(dv) : 0;
+        VIEWCHK(hipSetDevice(v->device));
+    }
+    memset(&v->info, 0, sizeof v->info);
+    v->info.cameras = num_cams, v->info.width = width, v->info.height = height, v->info.samples = samples;
+    v->info.filter = filter, v->info.num_texels = geo->numTexels, v->info.tiles = ntiles;
+    v->info.rays = (int64_t)num_cams * pix * spp;
+    v->info.bytes = cache_bytes(num_cams, width, height, samples, filter);
+    v->walls = ow;
+    VIEWCHK(v->records.alloc((size_t)v->info.bytes));
+    VIEWCHK(v->out_walls.alloc((size_t)std::max(nr, 1) * sizeof(OutWall)));
+    VIEWCHK(hipEventCreateWithFlags(&v->ev_tiles, hipEventDisableTiming));
+    VIEWCHK(hipEventCreateWithFlags(&v->ev_shade, hipEventDisableTiming));
+    for (auto &e : ev) VIEWCHK(hipEventCreate(&e));
+    VIEWCHK(d_rects.alloc(w.rects.size() * sizeof(RadRect)));
+    VIEWCHK(hipMemcpy(d_rects.p, w.rects.data(), w.rects.size() * sizeof(RadRect), hipMemcpyHostToDevice));
+    VIEWCHK(d_hits.alloc(w.hits.size() * sizeof(AoRect)));
+    VIEWCHK(hipMemcpy(d_hits.p, w.hits.data(), w.hits.size() * sizeof(AoRect), hipMemcpyHostToDevice));
+    VIEWCHK(d_first.alloc(w.first_tile.size() * 8));
+    VIEWCHK(hipMemcpy(d_first.p, w.first_tile.data(), w.first_tile.size() * 8, hipMemcpyHostToDevice));
+    VIEWCHK(d_cams.alloc((size_t)num_cams * sizeof(ViewCam)));
+    VIEWCHK(hipMemcpy(d_cams.p, vc.data(), (size_t)num_cams * sizeof(ViewCam), hipMemcpyHostToDevice));
+    VIEWCHK(d_keys.alloc((size_t)num_cams * w.sort_n * 8));
+    VIEWCHK(d_counts.alloc((size_t)num_cams * 4));
+    VIEWCHK(d_counters.alloc(16));
+    VIEWCHK(hipMemset(d_counters.p, 0, 16));
+    a.rects = d_rects.as<RadRect>();
+    a.hits = d_hits.as<AoRect>();
+    a.nrects = nr;
+    a.sort_n = w.sort_n;
+    a.width = width;
+    a.height = height;
+    a.first_tile = d_first.as<int64_t>();
+    a.tests = d_counters.as<unsigned long long>();
+    t.hits = d_counters.as<unsigned long long>() + 1;
+    s.samples = samples;
+    s.filter = filter;
+    for (int i = 0; i < samples; i++) s.offs[i] = (float)(2 * i + 1 - samples) / (float)(2 * samples);
+    /* every camera's candidate list, then the trace in launches of at most `budget` rays */
+    a.cams = d_cams.as<ViewCam>();
+    a.keys = d_keys.as<unsigned long long>();
+    a.counts = d_counts.as<int32_t>();
+    a.ncams = num_cams;
+    VIEWCHK(hipEventRecord(ev[0], nullptr));
+    VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    VIEWCHK(hipEventRecord(ev[1], nullptr));
+    for (int c0 = 0; c0 < num_cams; c0 += batch) {
+        a.ncams = std::min(batch, num_cams - c0);
+        a.cams = d_cams.as<ViewCam>() + c0;
+        a.keys = d_keys.as<unsigned long long>() + (size_t)c0 * w.sort_n;
+        a.counts = d_counts.as<int32_t>() + c0;
+        t.records = v->records.as<char>() + (size_t)c0 * spp * pix * rec;
+        for (s.y0 = 0; s.y0 < height; s.y0 += rows)
+            for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
+                s.y1 = std::min(height, s.y0 + rows);
+                s.x1 = std::min(width, s.x0 + cols);
+                VIEWCHK(fmgi_view_launch_trace(t, nullptr));
+            }
+    }
+    VIEWCHK(hipEventRecord(ev[2], nullptr));
+    VIEWCHK(hipEventSynchronize(ev[2]));
+    VIEWCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    v->info.cand_ms = ms;
+    VIEWCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    v->info.trace_ms = ms;
+    VIEWCHK(hipMemcpy(counters, d_counters.p, 16, hipMemcpyDeviceToHost));
+    v->info.tests = (int64_t)counters[0];
+    v->info.hits = (int64_t)counters[1];
+    *out = v;
+    v = nullptr;
+done:
+    for (auto &e : ev)
+        if (e) hipEventDestroy(e);
+    delete v; /* on an error: nothing stays allocated */
+    return rc;
+}
+
+int cache_tiles(fmgi_view_cache *v, const void *const *texels_dev, int num_sets, int spa, int tint,
+                void *const *tiles_dev, hipStream_t st) {
+    static const char fn[] = "fmgi_view_cache_tiles";
+    if (!v || !texels_dev || !tiles_dev) return arg_err(fn, "null argument");
+    if (num_sets < 1) return arg_err(fn, "num_sets < 1");
+    if (spa < 0) return arg_err(fn, "numSamplesPerArea < 0");
+    for (int k = 0; k < num_sets; k++)
+        if (!texels_dev[k] || !tiles_dev[k]) return arg_err(fn, "null set");
+    int rc = FMGI_OK;
+    OutArgs a;
+    memset(&a, 0, sizeof a);
+    if (v->info.tiles == 0) return FMGI_OK;
+    VIEWCHK(hipSetDevice(v->device));
+    if (spa != v->out_spa) { /* another normalisation: the table is rebuilt once its readers are through */
+        std::vector<OutWall> ow(v->walls.size());
+        for (size_t i = 0; i < ow.size(); i++) ow[i] = fmgi_out_wall(v->walls[i], spa);
+        if (v->tiles_pending) VIEWCHK(hipEventSynchronize(v->ev_tiles));
+        v->tiles_pending = false;
+        v->out_spa = -1;
+        VIEWCHK(hipMemcpy(v->out_walls.p, ow.data(), ow.size() * sizeof(OutWall), hipMemcpyHostToDevice));
+        v->out_spa = spa;
+    }
+    /* calls chain on the event, so its last record stands for every launch that reads the table */
+    if (v->tiles_pending) VIEWCHK(hipStreamWaitEvent(st, v->ev_tiles, 0));
+    a.walls = v->out_walls.as<OutWall>();
+    a.nwalls = (int)v->walls.size();
+    a.ntexels = v->info.tiles;
+    a.normalise = spa > 0;
+    a.tint_extra = tint != 0;
+    for (int k = 0; k < num_sets; k++) {
+        a.texels_in = (const float *)texels_dev[k];
+        a.rgb = (uint8_t *)tiles_dev[k];
+        VIEWCHK(fmgi_launch_output_const(a, st));
+    }
+    VIEWCHK(hipEventRecord(v->ev_tiles, st));
+    v->tiles_pending = true;
+done:
+    return rc;
+}
+
+int cache_shade(fmgi_view_cache *v, const void *const *tiles_dev, int num_sets, const uint8_t *background,
+                void *const *rgb_dev, void *coverage_dev, hipStream_t st) {
+    static const char fn[] = "fmgi_view_cache_shade";
+    if (!v || !tiles_dev || !rgb_dev || !background) return arg_err(fn, "null argument");
+    if (num_sets < 1) return arg_err(fn, "num_sets < 1");
+    for (int k = 0; k < num_sets; k++)
+        if (!tiles_dev[k] || !rgb_dev[k]) return arg_err(fn, "null set");
+    int rc = FMGI_OK;
+    const int64_t ntiles = v->info.tiles;
+    const int per_pass = std::min(num_sets, FMGI_VIEW_SETS);
+    ResolveArgs r;
+    memset(&r, 0, sizeof r);
+    VIEWCHK(hipSetDevice(v->device));
+    if (v->packed_sets < per_pass) { /* grow the scratch once nothing reads it any more */
+        if (v->shade_pending) VIEWCHK(hipEventSynchronize(v->ev_shade));
+        v->shade_pending = false;
+        hipFree(v->packed.p);
+        v->packed.p = nullptr;
+        v->packed_sets = 0;
+        VIEWCHK(v->packed.alloc((size_t)per_pass * (size_t)std::max<int64_t>(ntiles, 1) * 4));
+        v->packed_sets = per_pass;
+    }
+    /* an earlier call, maybe on another stream, may still read the scratch */
+    if (v->shade_pending) VIEWCHK(hipStreamWaitEvent(st, v->ev_shade, 0));
+    r.records = v->records.p;
+    r.ncams = v->info.cameras;
+    r.width = v->info.width;
+    r.height = v->info.height;
+    r.samples = v->info.samples;
+    r.filter = v->info.filter;
+    r.background = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
+    for (int k0 = 0; k0 < num_sets; k0 += FMGI_VIEW_SETS) {
+        r.nsets = std::min(FMGI_VIEW_SETS, num_sets - k0);
+        for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+            r.tiles[k] = nullptr;
+            r.rgb[k] = nullptr;
+        }
+        for (int k = 0; k < r.nsets; k++) {
+            uint32_t *words = v->packed.as<uint32_t>() + (size_t)k * (size_t)std::max<int64_t>(ntiles, 1);
+            VIEWCHK(fmgi_view_launch_pack((const uint8_t *)tiles_dev[k0 + k], words, ntiles, st));
+            r.tiles[k] = words;
+            r.rgb[k] = (uint8_t *)rgb_dev[k0 + k];
+        }
+        r.cov_out = k0 == 0 ? (uint8_t *)coverage_dev : nullptr;
+        VIEWCHK(fmgi_view_launch_resolve(r, st));
+    }
+    VIEWCHK(hipEventRecord(v->ev_shade, st));
+    v->shade_pending = true;
+done:
+    return rc;
+}
+
+} // namespace
+
+FMGI_API int64_t fmgi_view_cache_bytes(int num_cams, int width, int height, int samples, int filter) {
+    if (cache_shape_error(num_cams, true, width, height, samples, filter)) return 0;
+    return cache_bytes(num_cams, width, height, samples, filter);
+}
+
+FMGI_API int fmgi_view_cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
+                                    int height, int samples, int filter, fmgi_view_cache **out) {
+    return cache_create(geo, cams, num_cams, width, height, samples, filter, out);
+}
+
+FMGI_API void fmgi_view_cache_destroy(fmgi_view_cache *vc) {
+    if (!vc) return;
+    /* launches of tiles and shade may still read what the handle owns */
+    if (vc->tiles_pending) hipEventSynchronize(vc->ev_tiles);
+    if (vc->shade_pending) hipEventSynchronize(vc->ev_shade);
+    delete vc;
+}
+
+FMGI_API int fmgi_view_cache_info(const fmgi_view_cache *vc, struct fmgi_view_cache_info *out) {
+    if (!vc || !out) return arg_err("fmgi_view_cache_info", "null argument");
+    *out = vc->info;
+    return FMGI_OK;
+}
+
+FMGI_API int fmgi_view_cache_tiles(const fmgi_view_cache *vc, const void *const *texels_dev, int num_sets,
+                                   int numSamplesPerArea, int tintExtra, void *const *tiles_dev, void *stream) {
+    return cache_tiles(const_cast<fmgi_view_cache *>(vc), texels_dev, num_sets, numSamplesPerArea, tintExtra, tiles_dev,
+                       (hipStream_t)stream);
+}
+
+FMGI_API int fmgi_view_cache_shade(const fmgi_view_cache *vc, const void *const *tiles_dev, int num_sets,
+                                   const uint8_t background[3], void *const *rgb_dev, void *coverage_dev, void *stream) {
+    return cache_shade(const_cast<fmgi_view_cache *>(vc), tiles_dev, num_sets, background, rgb_dev, coverage_dev,
+                       (hipStream_t)stream);
+}
 
 FMGI_API int fmgi_shade_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
                               const uint8_t *tiles_rgb, const uint8_t background[3], int samples, int filter,

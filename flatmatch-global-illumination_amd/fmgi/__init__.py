@@ -23,7 +23,8 @@ HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and p
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
                    SPARSE_COUNT_BITS, SparseInfo, BakeSparseStats,
-                   VIEW_BILINEAR, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewStats, check, load)
+                   VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewStats, check,
+                   load)
 from .scene import RECT_DTYPE, Scene
 
 LAUNCH_DTYPE = np.dtype(
@@ -62,6 +63,9 @@ __all__ = [
     "shade_views",
     "view_candidates",
     "view_stats",
+    "ViewCache",
+    "view_cache_bytes",
+    "VIEW_CACHE_MAX_SETS",
     "Palette",
     "palette_table",
     "states_bytes",
@@ -863,3 +867,77 @@ def view_stats() -> dict:
     st = ViewStats()
     check(load().fmgi_view_stats(C.byref(st)), "fmgi_view_stats")
     return st.as_dict()
+
+
+# ---- traced views (include/flatmatch_gi.h) ------------------------------------------------
+
+def view_cache_bytes(num_cams: int, width: int, height: int, samples: int = 1, filter: str = "nearest") -> int:
+    """fmgi_view_cache_bytes: the device bytes of a ViewCache's records; 0 for arguments ViewCache rejects."""
+    if filter not in _VIEW_FILTERS:
+        raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
+    return int(load().fmgi_view_cache_bytes(num_cams, width, height, samples, _VIEW_FILTERS[filter]))
+
+
+def _ptr_array(ptrs):
+    ptrs = [int(p) for p in ptrs]
+    return (C.c_void_p * max(len(ptrs), 1))(*[C.c_void_p(p) for p in ptrs]), len(ptrs)
+
+
+class ViewCache:
+    """A traced view (fmgi_view_cache): shade_views' rays cast once, every sample's taps kept on the device.
+    tiles() runs the output step on device lightmaps and shade() gathers one picture per tile set, each what
+    output_tiles followed by shade_views gives, with no host round trip. Device buffers are integer addresses."""
+
+    def __init__(self, sc: Scene, cams, width: int, height: int, samples: int = 1, filter: str = "nearest"):
+        self.lib = load()
+        self.h = None
+        if filter not in _VIEW_FILTERS:
+            raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
+        cams = _cameras(cams)
+        g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+        h = C.c_void_p()
+        check(self.lib.fmgi_view_cache_create(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width, height,
+                                              samples, _VIEW_FILTERS[filter], C.byref(h)), "fmgi_view_cache_create")
+        del keep
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.lib.fmgi_view_cache_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        """fmgi_view_cache_info: the view's shape, the scene's tiles, rays, hits, tests, record bytes and times."""
+        st = ViewCacheInfo()
+        check(self.lib.fmgi_view_cache_info(self.h, C.byref(st)), "fmgi_view_cache_info")
+        return st.as_dict()
+
+    def tiles(self, texel_ptrs, spa: int, tile_ptrs, tint_extra: int = 0, stream: int = 0):
+        """fmgi_view_cache_tiles: tile_ptrs[k] (info()["tiles"] * 3 bytes) = output_tiles' RGB8 bytes for the device
+        texels float32 [num_texels][4] at texel_ptrs[k], which stay as they are. Asynchronous on `stream`."""
+        tp, n = _ptr_array(texel_ptrs)
+        op, m = _ptr_array(tile_ptrs)
+        if n != m:
+            raise FmgiError(f"tiles: {n} texel buffers for {m} tile buffers")
+        check(self.lib.fmgi_view_cache_tiles(self.h, tp, n, spa, tint_extra, op, C.c_void_p(stream or None)),
+              "fmgi_view_cache_tiles")
+
+    def shade(self, tile_ptrs, rgb_ptrs, background=(0, 0, 0), coverage_ptr: int = 0, stream: int = 0):
+        """fmgi_view_cache_shade: rgb_ptrs[k] (uint8 [cameras][height][width][3]) = shade_views' rgb for the device
+        tiles at tile_ptrs[k]; coverage_ptr (uint8 [cameras][height][width], or 0) = its coverage. Asynchronous on
+        `stream`."""
+        tp, n = _ptr_array(tile_ptrs)
+        rp, m = _ptr_array(rgb_ptrs)
+        if n != m:
+            raise FmgiError(f"shade: {n} tile buffers for {m} pictures")
+        bg = np.array(background, np.uint8)
+        assert bg.shape == (3,)
+        check(self.lib.fmgi_view_cache_shade(self.h, tp, n, bg.ctypes.data_as(C.c_void_p), rp,
+                                             C.c_void_p(coverage_ptr or None), C.c_void_p(stream or None)),
+              "fmgi_view_cache_shade")

@@ -70,6 +70,12 @@ EXPORTS = (
     "fmgi_view_candidates",
     "fmgi_view_stats",
     "fmgi_shade_views",
+    "fmgi_view_cache_bytes",
+    "fmgi_view_cache_create",
+    "fmgi_view_cache_destroy",
+    "fmgi_view_cache_info",
+    "fmgi_view_cache_tiles",
+    "fmgi_view_cache_shade",
     "fmgi_palette_reference",
     "fmgi_palette_table",
     "fmgi_states_bytes",
@@ -106,6 +112,7 @@ ACCUM_STREAM = 4
 VIEW_NEAREST = 0
 VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
+VIEW_CACHE_MAX_SETS = 8
 COLOUR_STATE_COUNT = 1024
 RECOLOUR_MAX_SCENARIOS = 8
 SPARSE_COUNT_BITS = 54
@@ -183,6 +190,32 @@ class ViewStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ViewCacheInfo(C.Structure):
+    """struct fmgi_view_cache_info (include/flatmatch_gi.h)."""
+
+    _fields_ = [
+        ("cameras", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("samples", C.c_int32),
+        ("filter", C.c_int32),
+        ("num_texels", C.c_int32),
+        ("tiles", C.c_int64),
+        ("rays", C.c_int64),
+        ("hits", C.c_int64),
+        ("tests", C.c_int64),
+        ("bytes", C.c_int64),
+        ("cand_ms", C.c_double),
+        ("trace_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(ViewCacheInfo) == 80
 
 
 class Palette(C.Structure):
@@ -353,6 +386,12 @@ def load() -> C.CDLL:
         "fmgi_view_candidates": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "fmgi_view_stats": (C.c_int, [C.POINTER(ViewStats)]),
         "fmgi_shade_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+        "fmgi_view_cache_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "fmgi_view_cache_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "fmgi_view_cache_destroy": (None, [vp]),
+        "fmgi_view_cache_info": (C.c_int, [vp, C.POINTER(ViewCacheInfo)]),
+        "fmgi_view_cache_tiles": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "fmgi_view_cache_shade": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
         "fmgi_palette_reference": (None, [C.POINTER(Palette)]),
         "fmgi_palette_table": (C.c_int, [C.POINTER(Palette), vp]),
         "fmgi_states_bytes": (C.c_size_t, [C.c_int]),

@@ -188,6 +188,45 @@ struct fmgi_view_stats {
 };
 int fmgi_view_stats(struct fmgi_view_stats *out);
 
+/* A traced view: fmgi_shade_views' rays are cast once and every sample's taps stay on the device;
+   any number of lighting scenarios is then shaded from device-resident lightmaps with no host round trip. Each
+   picture is, bit for bit, what fmgi_output_tiles followed by fmgi_shade_views gives for that lightmap. Like the
+   calls above the cache takes no fmgi_context; its device is FMGI_DEVICE (default 0).
+   create makes fmgi_shade_views' argument checks (geometry, image size, cameras, samples, filter, each camera)
+   and rejects num_cams < 1, a NULL out and a scene of 2^31 tiles or more, all FMGI_ERR_ARG before any device
+   call; then FMGI_ERR_NO_DEVICE; FMGI_ERR_OOM, with nothing left allocated, if the records do not fit. *out is
+   NULL after any error. geo->texels is not read and geo may be freed once create returns. The trace runs in
+   launches of at most 2^28 rays (FMGI_VIEW_RAYS_PER_LAUNCH in the environment lowers that). */
+#define FMGI_VIEW_CACHE_MAX_SETS 8 /* tile sets one gather pass carries; shade takes any number */
+typedef struct fmgi_view_cache fmgi_view_cache;
+struct fmgi_view_cache_info {
+    int32_t cameras, width, height, samples, filter, num_texels;
+    int64_t tiles;      /* level-0 tiles of all walls: fmgi_output_tile_bytes / 3 */
+    int64_t rays, hits; /* rays = cameras * width * height * samples^2; hits = rays that hit a wall */
+    int64_t tests;      /* intersects() evaluations of the trace (== fmgi_view_stats.tests of the same shade call) */
+    int64_t bytes;      /* device bytes of the records */
+    double cand_ms, trace_ms;
+};
+/* host only: cameras * width * height * samples^2 * (4 for NEAREST, 16 for BILINEAR); 0 for arguments create rejects */
+int64_t fmgi_view_cache_bytes(int num_cams, int width, int height, int samples, int filter);
+int  fmgi_view_cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                            int samples, int filter, fmgi_view_cache **out);
+void fmgi_view_cache_destroy(fmgi_view_cache *vc);            /* NULL is allowed; waits for the handle's launches */
+int  fmgi_view_cache_info(const fmgi_view_cache *vc, struct fmgi_view_cache_info *out);
+/* tiles and shade are asynchronous on `stream`; the pointer arrays and the background are read before they
+   return. FMGI_ERR_ARG for a NULL handle or pointer or num_sets < 1 (tiles: numSamplesPerArea < 0), before any
+   device call. Sets may not alias each other or the outputs. */
+/* tiles_dev[k] (device, tiles * 3 bytes) = the rgb_out of fmgi_output_tiles for this geometry with
+   texels = texels_dev[k] (device float [num_texels][4], read only, not normalised in place) */
+int  fmgi_view_cache_tiles(const fmgi_view_cache *vc, const void *const *texels_dev, int num_sets,
+                           int numSamplesPerArea, int tintExtra, void *const *tiles_dev, void *stream);
+/* rgb_dev[k] (device, [cameras][height][width][3]) = fmgi_shade_views' rgb_out for tiles_dev[k];
+   coverage_dev (device, [cameras][height][width], may be NULL) = its coverage_out. The sets are repacked to one
+   word per tile in scratch memory of the cache (4 B per tile and set of a pass); a later call's stream waits
+   for the earlier call before it reuses the scratch, without blocking the host. */
+int  fmgi_view_cache_shade(const fmgi_view_cache *vc, const void *const *tiles_dev, int num_sets,
+                           const uint8_t background[3], void *const *rgb_dev, void *coverage_dev, void *stream);
+
 /* ---- Build-defined device-resident API ---------------------------------------------------------- */
 enum {
     FMGI_OK = 0,

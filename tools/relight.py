@@ -282,7 +282,26 @@ def main(argv=None):
     if a.min_deposits > 0:
         print(f"  filtered: {a.min_deposits} deposits, radius <= {a.max_radius}, mean radius "
               f"{radii.float().mean().item():.3f}")
-    for name, t in zip(names, texels):
+    views = []
+    if a.view:
+        # the camera's rays are cast once; every scenario's picture is gathered from its device texels
+        vdev = f"cuda:{int(os.environ.get('FMGI_DEVICE', 0))}"  # the device of the geometry-based calls
+        vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter)
+        nbytes = max(3 * vc.info()["tiles"], 1)
+        vs = torch.cuda.Stream(device=vdev)
+        with torch.cuda.stream(vs):
+            for k0 in range(0, len(texels), fmgi.VIEW_CACHE_MAX_SETS):
+                part = [t.to(vdev) for t in texels[k0:k0 + fmgi.VIEW_CACHE_MAX_SETS]]
+                tiles_dev = [torch.empty(nbytes, dtype=torch.uint8, device=vdev) for _ in part]
+                rgb_dev = [torch.empty((a.height, a.width, 3), dtype=torch.uint8, device=vdev) for _ in part]
+                vc.tiles([t.data_ptr() for t in part], a.spa, [t.data_ptr() for t in tiles_dev], stream=vs.cuda_stream)
+                vc.shade([t.data_ptr() for t in tiles_dev], [t.data_ptr() for t in rgb_dev], tuple(a.background),
+                         stream=vs.cuda_stream)
+                views += rgb_dev
+        vs.synchronize()
+        views = [v.cpu().numpy() for v in views]
+        vc.close()
+    for k, (name, t) in enumerate(zip(names, texels)):
         d = os.path.join(a.output, name)
         os.makedirs(d, exist_ok=True)
         tex, tiles = fmgi.output_tiles(sc, t.cpu().numpy(), a.spa)
@@ -291,9 +310,7 @@ def main(argv=None):
         if a.view:
             from render_view import write_ppm
 
-            out = fmgi.shade_views(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, tiles,
-                                   tuple(a.background), samples=a.samples, filter=a.filter)
-            write_ppm(os.path.join(d, "view.ppm"), out["rgb"][0])
+            write_ppm(os.path.join(d, "view.ppm"), views[k])
         print(f"  {d}: mean texel {tex[:, :3].mean():.6g}")
     ctx.close()
 
