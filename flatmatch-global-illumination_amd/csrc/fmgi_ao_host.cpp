@@ -13,6 +13,12 @@
  *     (getPosition rectangle.c:476-505).
  * All geometry arithmetic is fp32 in the reference's order (this file is built with
  * -ffp-contract=off; x86-64 SSE, no FMA).
+ *
+ * One departure: the build stops at FMGI_AO_MAX_DEPTH levels and reports an error. The reference's
+ * rule has no end on some scenes with off-axis walls: a tilted rect's own corners can round to a
+ * non-zero distance from its own plane, so as a split plane it moves to a child with every other item
+ * of the node, that child picks it again, and the recursion repeats the same node for ever.
+ * Every tree of at most FMGI_AO_MAX_DEPTH levels is built exactly as before.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -80,11 +86,18 @@ struct Node {
 
 struct Tree {
     std::vector<Node> nodes;
-    int depth = 0;
+    bool too_deep = false; /* a node below FMGI_AO_MAX_DEPTH levels was needed: the build was abandoned */
 };
 
+const char *const kTooDeep = "BSP depth over FMGI_AO_MAX_DEPTH (48): the reference's build rule does not end on this scene "
+                             "(an off-axis wall that is not on its own plane in fp32), or the tree is deeper than "
+                             "the device traversal stack";
+
 void subdivide(Tree &t, const fmgi_rect *walls, int idx, int depth) {
-    t.depth = std::max(t.depth, depth + 1);
+    if (depth >= FMGI_AO_MAX_DEPTH) {
+        t.too_deep = true;
+        return;
+    }
     std::vector<int> items = t.nodes[idx].items;
     const int n = (int)items.size();
     if (n < 20) return; /* photonmap.c:312 */
@@ -124,6 +137,7 @@ void subdivide(Tree &t, const fmgi_rect *walls, int idx, int depth) {
         t.nodes[li].items = left;
         t.nodes[idx].left = li;
         subdivide(t, walls, li, depth + 1);
+        if (t.too_deep) return;
     }
     if (!right.empty()) {
         const int ri = (int)t.nodes.size();
@@ -202,13 +216,13 @@ int ao_run(const fmgi_geometry *geo, int wb, int we, fmgi_vec3 *texels_out) {
         if (lm[1] < 1 || lm[2] < 1 || lm[0] < 0 || (int64_t)lm[0] + (int64_t)lm[1] * lm[2] > geo->numTexels)
             return internal_set_err(FMGI_ERR_ARG, "fmgi_ambient_occlusion: a wall's texels lie outside numTexels");
     }
+    /* the tree is host work: a scene it cannot be built for is an argument error with or without a device */
+    const Tree tree = build_tree(walls, geo->numWalls);
+    if (tree.too_deep) return internal_set_err(FMGI_ERR_ARG, kTooDeep);
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0)
         return internal_set_err(FMGI_ERR_NO_DEVICE, "no HIP device visible");
 
-    const Tree tree = build_tree(walls, geo->numWalls);
-    if (tree.depth > FMGI_AO_MAX_DEPTH)
-        return internal_set_err(FMGI_ERR_ARG, "BSP tree deeper than the device traversal stack");
     std::vector<AoNode> nodes(tree.nodes.size());
     std::vector<AoRect> items;
     for (size_t i = 0; i < tree.nodes.size(); i++) {
@@ -398,6 +412,7 @@ FMGI_API int fmgi_geosphere(int levels, float *xyz, int cap) {
 FMGI_API int64_t fmgi_ao_tree(const fmgi_geometry *geo, int32_t *out, int64_t cap) {
     if (!geo || (geo->numWalls && !geo->walls)) return internal_set_err(FMGI_ERR_ARG, "fmgi_ao_tree: bad geometry");
     const Tree t = build_tree(geo->walls, geo->numWalls);
+    if (t.too_deep) return internal_set_err(FMGI_ERR_ARG, kTooDeep);
     std::vector<int32_t> enc;
     for (const Node &nd : t.nodes) {
         enc.push_back(nd.left);

@@ -84,7 +84,14 @@ int fmgi_dropin_reduce_order(int nshard, int32_t *dst, int32_t *src);
    cosine-weighted mean distance over the 481 geoSphere4 directions (misses count 10), traced through
    the reference's BSP tree. Same argument meaning and in-place update; a different name, because the
    reference's photonmap.o (which main.c also needs for performPhotonMappingNative) already defines
-   performAmbientOcclusionNative. Fatal errors print "[Err] ..." and exit(-1). */
+   performAmbientOcclusionNative. Fatal errors print "[Err] ..." and exit(-1).
+   Limitation: the BSP build stops at 48 levels (the device traversal stack). The reference's build
+   rule does not end on some scenes with off-axis walls: a tilted rect whose own corners are not on its
+   own plane in fp32 is handed, as the split plane, to a child together with every other item of the
+   node, and that child repeats the node (the reference recurses until it runs out of memory). Such a
+   scene is an error here -- FMGI_ERR_ARG with a message naming the BSP depth from
+   fmgi_ambient_occlusion and fmgi_ao_tree, before a device is looked for; the "[Err]" exit from
+   performAmbientOcclusionGpu -- never a crash. Axis-aligned scenes are not affected. */
 void performAmbientOcclusionGpu(fmgi_geometry *geo);
 /* Non-mutating form for walls [wall_begin, wall_end) (the BSP always spans every wall):
    texels_out = geo->texels with those walls' level-0 texels replaced. Returns 0 or FMGI_ERR_*. */
@@ -93,7 +100,7 @@ int fmgi_ambient_occlusion(const fmgi_geometry *geo, int wall_begin, int wall_en
    order, as xyz float triples; returns the count and copies at most `cap` directions. */
 int fmgi_geosphere(int levels, float *xyz, int cap);
 /* The AO BSP tree, encoded per node as {left, right, plane wall, n, n wall indices}; returns the
-   encoding's length and copies at most `cap` ints. */
+   encoding's length and copies at most `cap` ints, or FMGI_ERR_ARG for a scene over the depth bound. */
 int64_t fmgi_ao_tree(const fmgi_geometry *geo, int32_t *out, int64_t cap);
 
 /* ---- Output step: what main.c:66-95 does after the bake, minus the PNG encoding */

@@ -13,6 +13,11 @@
  *                      vector3_cl.c:152-160, transformToOrthoNormalBase photonmap.c:29-44
  * Arithmetic: IEEE fp32 in source order, no contraction (-ffp-contract=off), like the reference's
  * gcc -O2 -msse3 build. The direction table is an input (the caller's geoSphere4 table).
+ *
+ * The BSP build stops with an error at O_MAX_DEPTH levels (the product's FMGI_AO_MAX_DEPTH). The
+ * reference's subdivideNode has no end on scenes where an off-axis rect is not on its own plane in
+ * fp32 (scene.tilted_scene: the rect, picked as the split plane, lands in a child with all the node's
+ * items, and that child repeats the node); there is no reference result to restate there.
  */
 #include <math.h>
 #include <stdint.h>
@@ -73,8 +78,12 @@ static onode *o_node(int *items, int count) {
     return nd;
 }
 
-static void o_split(const orect *walls, onode *nd) {
-    if (nd->count < 20) return;
+#define O_MAX_DEPTH 48
+
+/* 0, or -1 when a node below O_MAX_DEPTH levels is needed */
+static int o_split(const orect *walls, onode *nd, int depth) {
+    if (depth >= O_MAX_DEPTH) return -1;
+    if (nd->count < 20) return 0;
     int best = nd->count, pick = 0;
     for (int i = 0; i < nd->count; i++) {
         int lo = 0, hi = 0, mid = 0;
@@ -103,14 +112,16 @@ static void o_split(const orect *walls, onode *nd) {
         else hi[nhi++] = nd->items[i];
         nd->items[i] = nd->items[--nd->count]; /* the vacated slot takes the last item */
     }
+    int rc = 0;
     if (nlo) {
         nd->lo = o_node(lo, nlo);
-        o_split(walls, nd->lo);
+        rc = o_split(walls, nd->lo, depth + 1);
     } else free(lo);
     if (nhi) {
         nd->hi = o_node(hi, nhi);
-        o_split(walls, nd->hi);
+        if (rc == 0) rc = o_split(walls, nd->hi, depth + 1);
     } else free(hi);
+    return rc;
 }
 
 static void o_free(onode *nd) {
@@ -176,7 +187,7 @@ static int o_find(const orect *walls, const onode *nd, o3 src, o3 dir, float *di
 
 /*
  * AO of walls [wb, we): texels (float4 x num_texels) get (d, d, d, 0) on those walls' level-0 texels.
- * dirs: ndirs xyz triples. Returns 0.
+ * dirs: ndirs xyz triples. Returns 0, or -1 (texels untouched) when the BSP build exceeds O_MAX_DEPTH.
  */
 int ao_oracle(const void *walls_v, int nwalls, int wb, int we, const float *dirs, int ndirs, float *texels,
               int nthreads) {
@@ -184,7 +195,10 @@ int ao_oracle(const void *walls_v, int nwalls, int wb, int we, const float *dirs
     int *all = (int *)malloc(sizeof(int) * (nwalls ? nwalls : 1));
     for (int i = 0; i < nwalls; i++) all[i] = i;
     onode *root = o_node(all, nwalls);
-    o_split(walls, root);
+    if (o_split(walls, root, 0) != 0) {
+        o_free(root);
+        return -1;
+    }
     float fsum = 0;
     for (int k = 0; k < ndirs; k++) fsum += dirs[3 * k + 2];
     for (int wi = wb; wi < we; wi++) {
@@ -249,7 +263,10 @@ int64_t ao_oracle_tree(const void *walls_v, int nwalls, int32_t *out, int64_t ca
     int *all = (int *)malloc(sizeof(int) * (nwalls ? nwalls : 1));
     for (int i = 0; i < nwalls; i++) all[i] = i;
     onode *root = o_node(all, nwalls);
-    o_split(walls, root);
+    if (o_split(walls, root, 0) != 0) { /* deeper than O_MAX_DEPTH */
+        o_free(root);
+        return -1;
+    }
     int64_t len = 0;
     int next = 0;
     o_enc(root, out, &len, cap, &next);

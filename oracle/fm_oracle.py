@@ -313,6 +313,14 @@ def ref_run_items(scene, source: int, is_window: int, rng_states, variant: str =
     return out
 
 
+class BspDepthError(RuntimeError):
+    """The AO BSP build went past the depth bound (ao_oracle.c O_MAX_DEPTH): the reference's build rule has
+    no end on this scene."""
+
+
+BSP_DEPTH_MESSAGE = "ao_oracle: BSP depth over 48, the reference's build rule does not end on this scene"
+
+
 def ambient_occlusion(scene, wall_begin: int = 0, wall_end: int | None = None, dirs=None, nthreads: int = 0):
     """The reference's performAmbientOcclusionNative restated (ao_oracle.c) on walls [wall_begin,
     wall_end): float32 [numTexels, 4] texels, zero except those walls' level-0 texels. `dirs` is the
@@ -325,7 +333,8 @@ def ambient_occlusion(scene, wall_begin: int = 0, wall_end: int | None = None, d
     d = np.ascontiguousarray(geosphere.generate(4) if dirs is None else dirs, dtype=np.float32)
     tex = np.zeros((scene.num_texels, 4), np.float32)
     threads = nthreads or int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
-    lib.ao_oracle(_p(walls), len(walls), wall_begin, we, _p(d), len(d), _p(tex), threads)
+    if lib.ao_oracle(_p(walls), len(walls), wall_begin, we, _p(d), len(d), _p(tex), threads) != 0:
+        raise BspDepthError(BSP_DEPTH_MESSAGE)
     return tex
 
 
@@ -334,6 +343,8 @@ def ao_tree(scene) -> np.ndarray:
     lib = load()
     walls = np.ascontiguousarray(scene.walls)
     n = lib.ao_oracle_tree(_p(walls), len(walls), None, 0)
+    if n < 0:
+        raise BspDepthError(BSP_DEPTH_MESSAGE)
     out = np.zeros(max(n, 1), np.int32)
     lib.ao_oracle_tree(_p(walls), len(walls), _p(out), n)
     return out[:n]

@@ -5,7 +5,12 @@ and oracle/_ref/ao_ref built by oracle/build_ref.sh).
 For each scene, oracle/_ref/ao_ref runs the reference's own performAmbientOcclusionNative
 (photonmap.c:478-490, compiled from /root/reference) on the geometry; the fixture keeps the SHA-256 of
 the float32 [numTexels, 4] result, its sum, and the first level-0 texel of every wall (so a mismatch
-can be located). tests/test_ao.py checks the oracle restatement against it."""
+can be located). tests/test_ao.py checks the oracle restatement against it.
+
+Off-axis and partitioned scenes (tests/offaxis_scenes.py): `crossing` and `tilted56` are recorded. The
+reference does not finish on tilted1 and open_tilted (still recursing in subdivideNode after 120 s) or
+tilted12 (segmentation fault after 6 s): its BSP build has no end there, so they have no
+entry."""
 import hashlib
 import json
 import os
@@ -17,7 +22,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd")]
+sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd"), os.path.join(REPO, "tests")]
+import offaxis_scenes  # noqa: E402
 from fmgi import scene  # noqa: E402
 
 
@@ -33,6 +39,8 @@ def main():
     scenes = {
         "box8": scene.box_scene(8),
         "example": scene.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example"),
+        "crossing": offaxis_scenes.get("crossing"),
+        "tilted56": offaxis_scenes.get("tilted56"),
     }
     if "--box200" in sys.argv:
         scenes["box200"] = scene.box_scene(200)

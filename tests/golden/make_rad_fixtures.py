@@ -21,7 +21,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd")]
+sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd"), os.path.join(REPO, "tests")]
+import offaxis_scenes  # noqa: E402
 from fmgi import scene  # noqa: E402
 
 
@@ -39,6 +40,10 @@ def main():
     scenes = {
         "box200_t2_lit": (scene.box_scene(200, tile_size=2.0, with_light=True), 7),
         "box200_t2": (scene.box_scene(200, tile_size=2.0), 1),
+        # tests/offaxis_scenes.py: partitions, tilted rects, and a scene without a ceiling (rays that miss)
+        "crossing": (offaxis_scenes.get("crossing"), 3),
+        "open_tilted": (offaxis_scenes.get("open_tilted"), 5),
+        "tilted12": (offaxis_scenes.get("tilted12"), 9),
     }
     if "--example" in sys.argv:
         scenes = {"example": (scene.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example"), 1)}

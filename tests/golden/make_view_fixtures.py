@@ -10,7 +10,11 @@ camera, the candidate list (wall index, minDistance bits), the per-pixel wall / 
 the number of intersects() evaluations. tests/test_view.py checks a numpy restatement and the GPU against
 it. The counts below were measured with the reference objects and are asserted here.
 
-  python tests/golden/make_view_fixtures.py
+tests/golden/view_ref_offaxis.npz holds, in the same layout, two cameras each on the partitioned, tilted and open
+scenes of tests/offaxis_scenes.py (tests/test_offaxis_views.py), one of them looking along a tilted panel.
+
+  python tests/golden/make_view_fixtures.py            (view_ref.npz)
+  python tests/golden/make_view_fixtures.py offaxis    (view_ref_offaxis.npz)
 """
 import json
 import os
@@ -22,7 +26,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd")]
+sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd"), os.path.join(REPO, "tests")]
+import offaxis_scenes  # noqa: E402
 from fmgi import scene  # noqa: E402
 
 REF = os.environ.get("FMGI_REFERENCE", "/root/reference")
@@ -52,8 +57,26 @@ CASES = {
     "box8_C": ("box8", CAM_C, 5, 2565, 14645),
 }
 
+# 64 x 48 cameras on tests/offaxis_scenes.py. GRAZE stands 1.2 m before the first tilted panel of tilted12 (wall 200;
+# wall 164 of open_tilted), 0.05 m off its plane on the lit side, and looks along its width: its rays meet the panel
+# at 1.7 to 2.4 degrees. SKY looks up and out of the scene without a ceiling; P stands off both partition planes.
+GRAZE = ((1.6349, 3.0702, 0.7), (0.6044, 0.7967, 0), (0, 0, 1), 0.02, 64, 48)
+SKY = ((5, 4, 1.3), (1, 0.5, 0.6), (0, 0, 1), 0.02, 64, 48)
+CAM_P = ((8.5, 6.8, 1.3), (-1, -0.6, -0.1), (0, 0, 1), 0.02, 64, 48)
+CAM_C64 = ((5, 4, 20), (0, 0, -1), (0, 1, 0), 0.01, 64, 48)
+OFFAXIS_CASES = {
+    "crossing_P": ("crossing", CAM_P, 192, 3072, 152817),
+    "crossing_C": ("crossing", CAM_C64, 180, 2565, 485120),
+    "tilted12_graze": ("tilted12", GRAZE, 168, 3072, 92229),
+    "tilted12_A": ("tilted12", CAM_A, 115, 3072, 225003),
+    "open_tilted_graze": ("open_tilted", GRAZE, 135, 2904, 82340),
+    "open_tilted_sky": ("open_tilted", SKY, 91, 727, 263228),
+}
+
 
 def get_scene(name):
+    if name in offaxis_scenes.NAMES:
+        return offaxis_scenes.get(name)
     if name == "example":
         return scene.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example")
     return {"box200": lambda: scene.box_scene(200, tile_size=2.0), "box2000": lambda: scene.box_scene(2000, tile_size=2.0),
@@ -96,10 +119,11 @@ def run(exe, tmp, sc, cam):
 
 
 def main():
+    offaxis = sys.argv[1:] == ["offaxis"]
     out, meta, scenes = {}, {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         exe = build(tmp)
-        for name, (sname, cam, ncand, hits, tests) in CASES.items():
+        for name, (sname, cam, ncand, hits, tests) in (OFFAXIS_CASES if offaxis else CASES).items():
             sc = scenes.setdefault(sname, get_scene(sname))
             r = run(exe, tmp, sc, cam)
             got = (len(r["cand_wall"]), int((r["wall"] >= 0).sum()), int(r["tests"]))
@@ -111,7 +135,7 @@ def main():
             out[f"{name}.camera"] = camera_words(cam)
             meta[name] = {"scene": sname, "width": cam[4], "height": cam[5]}
     out["meta"] = np.array(json.dumps(meta))
-    np.savez_compressed(os.path.join(HERE, "view_ref.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, "view_ref_offaxis.npz" if offaxis else "view_ref.npz"), **out)
 
 
 if __name__ == "__main__":
