@@ -23,8 +23,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(REPO, "oracle"), os.path.join(REPO, "flatmatch-global-illumination_amd")]
+sys.path[:0] = [os.path.join(REPO, "oracle"), os.path.join(REPO, "flatmatch-global-illumination_amd"),
+                os.path.join(REPO, "tests")]
 
+import bake_scenes  # noqa: E402
 import fm_oracle as O  # noqa: E402
 from fmgi import scene as S  # noqa: E402
 
@@ -55,24 +57,29 @@ def main():
     summary = {}
     example = S.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example")
     apartment = S.load_geometry(os.path.join(HERE, "apartment30_geometry.bin"), "apartment30")
-    cases = [  # (fixture name, scene, spa, [(launch index, gids)])
-        ("example", example, 65_000, [(0, range(0, 96)), (7, range(0, 32))]),
-        ("box200", S.box_scene(200), 172_413_793, [(0, range(1000, 1048))]),
+    both = ("strict", "relaxed")
+    cases = [  # (fixture name, scene, spa, [(launch index, gids)], variants)
+        ("example", example, 65_000, [(0, range(0, 96)), (7, range(0, 32))], both),
+        ("box200", S.box_scene(200), 172_413_793, [(0, range(1000, 1048))], both),
         # BASELINE config 2 schedule (43 launches): late launches, rng offsets deep in the glibc prefix
-        ("example_late", example, 6_500_000, [(40, range(0, 32)), (42, range(10_400, 10_432))]),
+        ("example_late", example, 6_500_000, [(40, range(0, 32)), (42, range(10_400, 10_432))], both),
         # BASELINE config 4 schedule (3,907 launches): the last two launches
-        ("box200_late", S.box_scene(200), 1_724_137_931, [(3905, range(0, 32)), (3906, range(6_600, 6_632))]),
+        ("box200_late", S.box_scene(200), 1_724_137_931, [(3905, range(0, 32)), (3906, range(6_600, 6_632))], both),
         # BASELINE config 5 (2000 rects): the first and the last launch
-        ("box2000", S.box_scene(2000), 172_413_793, [(0, range(1000, 1032)), (390, range(16_000, 16_032))]),
+        ("box2000", S.box_scene(2000), 172_413_793, [(0, range(1000, 1032)), (390, range(16_000, 16_032))], both),
         # generated 30-room layout (654 walls, 34 sources): a window launch and the last light launch
-        ("apartment30", apartment, 3_000_000, [(0, range(0, 32)), (77, range(19_900, 19_932))]),
+        ("apartment30", apartment, 3_000_000, [(0, range(0, 32)), (77, range(19_900, 19_932))], both),
     ]
+    # tests/bake_scenes.py (strict only): most photons escaping, rects that are not axis-aligned, and 15 coincident
+    # rects, whose hits the kernel's index-order scan gives to the first of them
+    cases += [(name, bake_scenes.get(name), bake_scenes.SPA, [(0, range(0, 32))], ("strict",))
+              for name in ("open_box", "tilted12", "stacked14")]
     only = os.environ.get("FMGI_REF_CASES")  # e.g. "box2000,apartment30": regenerate a subset
     if only:
         cases = [c for c in cases if c[0] in only.split(",")]
-    for name, sc, spa, parts in cases:
+    for name, sc, spa, parts, variants in cases:
         L = O.schedule_with_offsets(sc, spa, offs)
-        for variant in ("strict", "relaxed"):
+        for variant in variants:
             acc = {}
             n_same = n_tot = 0
             worst = 0.0

@@ -173,6 +173,9 @@ def test_config5_full_size_properties_and_late_window(torch_cuda, box2000, offse
     assert 100 * n >= 1_000_000_000
     ctx.reset_stats()
     full = _bake_gpu(torch_cuda, ctx, 0, n)
+    # the default bake of config 5 is the compact closed box's instance (not the general grid scan it would
+    # silently fall to if build_compact refused the scene)
+    assert "ScanGridT<true,true,true>" in ctx.last_bake_kernel.replace(" ", ""), ctx.last_bake_kernel
     st = ctx.stats()
     assert st["photons"] == 100 * n
     assert st["deposits"] + st["escapes"] == st["scans"]
