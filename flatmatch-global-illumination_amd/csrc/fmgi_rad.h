@@ -16,6 +16,8 @@
  *   k_rad_gather one lane per job: the sequential fp32 sum over its 10000 source texels;
  *   k_rad_update src = src*0.7f + dest*(0.3f/10000) on every texel;
  *   k_rad_mip    one workgroup per rectangle: rectangle.c:508-575 mipmap, level by level.
+ * fmgi_rad_cache_*  keeps the first two kernels' result, the rays' texel ids, on the device and runs
+ * the last three for any emitter palettes, several at a time, over an interleaved table (fmgi_rad_solve.hip).
  */
 #ifndef FMGI_RAD_H
 #define FMGI_RAD_H
@@ -31,6 +33,11 @@
 #define FMGI_RAD_SUBS 8       /* rand sub-streams per job */
 #define FMGI_RAD_SUBLEN 2500  /* FMGI_RAD_DRAWS / FMGI_RAD_SUBS */
 #define FMGI_RAD_ITERS 7      /* bounce iterations, radiosityNative.c:230 */
+#define FMGI_RAD_REFLECTANCE 0.3f /* radiosityNative.c:103 */
+#define FMGI_RAD_WINDOW 30.0f     /* a window texel's start, all channels (radiosityNative.c:139) */
+#define FMGI_RAD_LIGHT_R 28.0f    /* a light texel's start (radiosityNative.c:142) */
+#define FMGI_RAD_LIGHT_G 28.0f
+#define FMGI_RAD_LIGHT_B 32.0f
 #define FMGI_RAD_MAX_SORT 16384 /* candidate sort capacity (LDS keys of 8 B) */
 #define FMGI_RAD_JUMP_BITS 40 /* jump matrices M^(2500 * 2^b), b < 40 */
 
@@ -82,8 +89,30 @@ struct RadBounce {
     float keep, gain;    /* 1 - reflectance, reflectance / 10000 */
 };
 
+/* a pass of fmgi_rad_cache_solve (fmgi_rad_solve.hip): RadBounce over `[texel][kp]` float4 tables */
+struct RadSolve {
+    const int32_t *sids;
+    const RadJob *jobs;
+    int64_t njobs;
+    const RadRect *rects;
+    int nrects;
+    int kp;              /* slots per texel: 1, 2, 4 or 8 */
+    int64_t ntex;        /* texels incl. the window/light texels */
+    int64_t num_texels;  /* the walls' texels: what a solve returns */
+    const float4 *src;
+    float4 *dst;         /* next src; the table k_rad_init_sets fills */
+    float4 *dest;        /* the gather sums (zero except job texels) */
+    float keep, gain;
+};
+
 hipError_t fmgi_rad_launch_rand(const RadArgs &a, hipStream_t s);
 hipError_t fmgi_rad_launch_rays(const RadArgs &a, hipStream_t s);
 hipError_t fmgi_rad_launch_bounce(const RadBounce &b, hipStream_t s);
+/* emit_dev: float [nsets][nemit][3]; rects [first_emit, first_emit + nemit) are the windows, then the lights */
+hipError_t fmgi_rad_launch_init_sets(const RadSolve &b, const float *emit_dev, int nsets, int nemit, int first_emit,
+                                     hipStream_t s);
+hipError_t fmgi_rad_launch_bounce_sets(const RadSolve &b, hipStream_t s);
+/* out_dev: device array of nsets pointers to float [num_texels][4] */
+hipError_t fmgi_rad_launch_unpack_sets(const RadSolve &b, void *const *out_dev, int nsets, hipStream_t s);
 
 #endif

@@ -24,6 +24,7 @@ from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
                    SPARSE_COUNT_BITS, SparseInfo, BakeSparseStats,
                    VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewStats, check,
+                   RAD_CACHE_MAX_ITERATIONS, RAD_CACHE_MAX_SETS, RadCacheInfo,
                    load)
 from .scene import RECT_DTYPE, Scene
 
@@ -66,6 +67,11 @@ __all__ = [
     "ViewCache",
     "view_cache_bytes",
     "VIEW_CACHE_MAX_SETS",
+    "RadCache",
+    "rad_cache_bytes",
+    "rad_reference_emit",
+    "RAD_CACHE_MAX_SETS",
+    "RAD_CACHE_MAX_ITERATIONS",
     "Palette",
     "palette_table",
     "states_bytes",
@@ -730,6 +736,96 @@ def radiosity_stats() -> dict:
     st = RadStats()
     check(lib.fmgi_radiosity_stats(C.byref(st)), "fmgi_radiosity_stats")
     return st.as_dict()
+
+
+# ---- radiosity scenarios (include/flatmatch_gi.h) ------------------------------------------
+
+def rad_cache_bytes(sc: Scene) -> int:
+    """fmgi_rad_cache_bytes: the device bytes a RadCache of the scene keeps (ids, jobs, rectangles)."""
+    g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+    n = int(check(load().fmgi_rad_cache_bytes(C.byref(g)), "fmgi_rad_cache_bytes"))
+    del keep
+    return n
+
+
+def rad_reference_emit(sc: Scene) -> np.ndarray:
+    """fmgi_rad_reference_emit: the reference's palette, float32 [windows + lights, 3]: 30 for every window,
+    (28, 28, 32) for every light."""
+    g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+    emit = np.zeros((len(sc.windows) + len(sc.lights), 3), np.float32)
+    check(load().fmgi_rad_reference_emit(C.byref(g), _ptr(emit)), "fmgi_rad_reference_emit")
+    del keep
+    return emit
+
+
+class RadCache:
+    """A radiosity cache (fmgi_rad_cache): radiosity()'s rays cast once from the current libc rand() position,
+    their source texel ids kept on the device. solve() runs the bounces for any number of emitter palettes and
+    leaves the texels on the device, where ViewCache.tiles reads them (spa = 0, tint_extra = 1)."""
+
+    def __init__(self, sc: Scene):
+        self.lib = load()
+        self.h = None
+        self.num_texels = sc.num_texels
+        self.emitters = len(sc.windows) + len(sc.lights)
+        g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
+        h = C.c_void_p()
+        check(self.lib.fmgi_rad_cache_create(C.byref(g), C.byref(h)), "fmgi_rad_cache_create")
+        del keep
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.lib.fmgi_rad_cache_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def info(self) -> dict:
+        """fmgi_rad_cache_info: jobs, rects, windows, lights, texels (the emitters' included), rays, bytes and the
+        trace's rand_ms and rays_ms."""
+        st = RadCacheInfo()
+        check(self.lib.fmgi_rad_cache_info(self.h, C.byref(st)), "fmgi_rad_cache_info")
+        return st.as_dict()
+
+    def sids(self) -> np.ndarray:
+        """fmgi_rad_cache_sids: int32 [jobs, 10000], radiosity(with_sids=True)'s rows."""
+        out = np.zeros((self.info["jobs"], 10000), np.int32)
+        check(self.lib.fmgi_rad_cache_sids(self.h, _ptr(out)), "fmgi_rad_cache_sids")
+        return out
+
+    def solve(self, emit, iterations: int = 7, stream=None):
+        """fmgi_rad_cache_solve: emit float32 [K, windows + lights, 3] (one set may come as [emitters, 3]) ->
+        a torch float32 device tensor [K, numTexels, 4]. Asynchronous on `stream`: a torch.cuda.Stream, a
+        hipStream_t integer, or None for torch's current stream."""
+        import os
+
+        import torch
+
+        emit = np.ascontiguousarray(emit, np.float32)
+        if emit.ndim == 2:
+            emit = emit[None]
+        if emit.ndim != 3 or emit.shape[1:] != (self.emitters, 3):
+            raise FmgiError(f"emit has shape {emit.shape}, the scene's palettes are [K, {self.emitters}, 3]")
+        k = emit.shape[0]
+        dev = torch.device("cuda", int(os.environ.get("FMGI_DEVICE", "0")))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        out = torch.empty((k, self.num_texels, 4), dtype=torch.float32, device=dev)
+        if isinstance(stream, int):
+            handle = stream
+        else:
+            handle = stream.cuda_stream
+            out.record_stream(stream)
+        ptrs, n = _ptr_array(out[i].data_ptr() for i in range(k))
+        check(self.lib.fmgi_rad_cache_solve(self.h, emit.ctypes.data_as(C.c_void_p), n, iterations, ptrs,
+                                            C.c_void_p(handle or None)), "fmgi_rad_cache_solve")
+        return out
 
 
 def geosphere(levels: int = 4) -> np.ndarray:

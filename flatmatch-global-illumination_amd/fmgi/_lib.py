@@ -66,6 +66,13 @@ EXPORTS = (
     "fmgi_radiosity_jobs",
     "fmgi_radiosity_stats",
     "fmgi_rand_skip",
+    "fmgi_rad_cache_bytes",
+    "fmgi_rad_cache_create",
+    "fmgi_rad_cache_destroy",
+    "fmgi_rad_cache_info",
+    "fmgi_rad_cache_sids",
+    "fmgi_rad_reference_emit",
+    "fmgi_rad_cache_solve",
     "fmgi_render_views",
     "fmgi_view_candidates",
     "fmgi_view_stats",
@@ -113,6 +120,8 @@ VIEW_NEAREST = 0
 VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
 VIEW_CACHE_MAX_SETS = 8
+RAD_CACHE_MAX_SETS = 8
+RAD_CACHE_MAX_ITERATIONS = 64
 COLOUR_STATE_COUNT = 1024
 RECOLOUR_MAX_SCENARIOS = 8
 SPARSE_COUNT_BITS = 54
@@ -173,6 +182,28 @@ class RadStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RadCacheInfo(C.Structure):
+    """struct fmgi_rad_cache_info (include/flatmatch_gi.h)."""
+
+    _fields_ = [
+        ("jobs", C.c_int64),
+        ("rects", C.c_int64),
+        ("windows", C.c_int64),
+        ("lights", C.c_int64),
+        ("texels", C.c_int64),
+        ("rays", C.c_int64),
+        ("bytes", C.c_int64),
+        ("rand_ms", C.c_double),
+        ("rays_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(RadCacheInfo) == 72
 
 
 class ViewStats(C.Structure):
@@ -382,6 +413,13 @@ def load() -> C.CDLL:
         "fmgi_radiosity_jobs": (i64, [vp]),
         "fmgi_radiosity_stats": (C.c_int, [C.POINTER(RadStats)]),
         "fmgi_rand_skip": (C.c_int, [C.c_uint64]),
+        "fmgi_rad_cache_bytes": (i64, [vp]),
+        "fmgi_rad_cache_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "fmgi_rad_cache_destroy": (None, [vp]),
+        "fmgi_rad_cache_info": (C.c_int, [vp, C.POINTER(RadCacheInfo)]),
+        "fmgi_rad_cache_sids": (C.c_int, [vp, vp]),
+        "fmgi_rad_reference_emit": (C.c_int, [vp, vp]),
+        "fmgi_rad_cache_solve": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
         "fmgi_render_views": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
         "fmgi_view_candidates": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "fmgi_view_stats": (C.c_int, [C.POINTER(ViewStats)]),

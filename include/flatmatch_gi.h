@@ -142,6 +142,55 @@ int fmgi_radiosity_stats(fmgi_rad_stats *out);
    radiosity backend uses (as n rand() calls would). Returns 0 or FMGI_ERR_ARG (not glibc TYPE_3). */
 int fmgi_rand_skip(uint64_t n);
 
+/* ---- Radiosity scenarios ------------------------------------------------------------- */
+/* A radiosity cache of a geometry holds the rectangle list (walls, windows, lights; the windows' and lights'
+   texels appended after numTexels, radiosityNative.c:108-131), the jobs (one per level-0 wall texel) and the
+   sourceTexelIds of every ray: exactly the values fmgi_radiosity computes from the caller's libc rand() position.
+   fmgi_rad_cache_create consumes the stream exactly as fmgi_radiosity does (20000 x jobs draws); on failure it
+   puts the stream back. fmgi_rad_cache_solve draws nothing.
+
+   A palette is emit[k][e][3], e over the windows and then the lights, every value finite and >= 0. Scenario k's
+   result is what radiosityNative.c:139-149, 230-251 computes when every texel of emitter e, mip levels included,
+   starts at emit[k][e] (the reference: 30 for windows, (28, 28, 32) for lights) and the walls' texels at 0:
+   `iterations` rounds of gather (the sequential fp32 sum over rays 0..9999, skipping -1), update
+   (src * 0.7f + dest * (0.3f / 10000), not contracted) and mipmap (rectangle.c:508-575), in the reference's
+   operations and order. The output is texels [0, numTexels) with w = 0. With fmgi_rad_reference_emit's palette
+   and iterations = 7 it equals fmgi_radiosity's bit for bit. A set's result depends neither on the other sets of
+   the call nor on their number.
+
+   Argument errors are found on the host before any device call: FMGI_ERR_ARG for a NULL handle, geometry or
+   pointer, num_sets < 1, iterations outside 1..FMGI_RAD_CACHE_MAX_ITERATIONS, an emit value that is negative, NaN
+   or infinite, and a geometry fmgi_radiosity rejects; FMGI_ERR_ARG if libc rand() is not in glibc's TYPE_3 state;
+   then FMGI_ERR_NO_DEVICE. */
+#define FMGI_RAD_CACHE_MAX_SETS 8        /* palettes one pass carries; solve takes any number */
+#define FMGI_RAD_CACHE_MAX_ITERATIONS 64
+typedef struct fmgi_rad_cache fmgi_rad_cache;
+struct fmgi_rad_cache_info {
+    int64_t jobs, rects, windows, lights;
+    int64_t texels;                    /* includes the window/light texels */
+    int64_t rays;                      /* 10000 x jobs */
+    int64_t bytes;                     /* fmgi_rad_cache_bytes */
+    double rand_ms, rays_ms;           /* create's device phases, as fmgi_rad_stats */
+};
+/* Host only: the device bytes create keeps: 40000 per job for the ids, 64 per job and 64 per rectangle.
+   FMGI_ERR_ARG (negative) for a geometry fmgi_radiosity rejects. */
+int64_t fmgi_rad_cache_bytes(const fmgi_geometry *geo);
+int  fmgi_rad_cache_create(const fmgi_geometry *geo, fmgi_rad_cache **out); /* *out is NULL on failure */
+void fmgi_rad_cache_destroy(fmgi_rad_cache *rc);               /* NULL is allowed; waits for the handle's launches */
+int  fmgi_rad_cache_info(const fmgi_rad_cache *rc, struct fmgi_rad_cache_info *out);
+/* sids_out (jobs x 10000 int32): the rows in the reference's per-texel order, as fmgi_radiosity's sids_out */
+int  fmgi_rad_cache_sids(const fmgi_rad_cache *rc, int32_t *sids_out);
+/* Host only: emit[windows + lights][3] = the reference's palette */
+int  fmgi_rad_reference_emit(const fmgi_geometry *geo, float *emit);
+/* texels_dev[k]: device float [numTexels][4], the layout fmgi_view_cache_tiles reads (the radiosity mode uses
+   numSamplesPerArea = 0, tintExtra = 1, main.c:88-91). Asynchronous on `stream` (a hipStream_t, NULL: the default
+   stream); emit and the pointer array are read before the call returns. emit may be NULL for a geometry without
+   windows and lights. The scratch (three tables of 16 B x texels x the sets of a pass) belongs to the handle and
+   is guarded by an event: a later call's stream waits for the earlier call, the host does not, unless the scratch
+   has to grow. More than FMGI_RAD_CACHE_MAX_SETS sets run in further passes. */
+int  fmgi_rad_cache_solve(const fmgi_rad_cache *rc, const float *emit, int num_sets, int iterations,
+                          void *const *texels_dev, void *stream);
+
 /* ---- View renderer ------------------------------------------------------------ */
 /* The reference's debug raycaster (debugRaytracer.cc:121-176) on the GPU, for any pin-hole camera and for
    batches of cameras. dir has any non-zero length, up is used as given, pixel is the size of one pixel on
