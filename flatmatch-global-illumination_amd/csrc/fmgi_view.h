@@ -109,6 +109,29 @@ struct ResolveArgs {
     uint32_t background; /* r | g << 8 | b << 16 */
 };
 
+/*
+ * The orthographic and equirectangular cameras (fmgi_*_proj). Their ViewCam holds an orthonormal
+ * frame: d = f = normalized(dir), r = normalized(cross(f, up)), u = cross(r, f), c = pos + f. The kernels are
+ * instances of k_view_candidates_proj, k_view_shade_proj and k_view_trace_proj; the pin-hole keeps its own.
+ */
+#define FMGI_VIEW_PINHOLE 0 /* FMGI_PROJ_* of the C ABI */
+#define FMGI_VIEW_ORTHO 1
+#define FMGI_VIEW_EQUIRECT 2
+
+struct ShadeProjArgs {
+    ShadeArgs s;
+    float kphi, ktheta; /* EQUIRECT: radians per pixel column and row, 2 pi / width and pi / height */
+};
+
+struct TraceProjArgs {
+    TraceArgs t;
+    float kphi, ktheta;
+};
+
+hipError_t fmgi_view_launch_candidates_proj(const ViewArgs &a, int projection, hipStream_t s);
+hipError_t fmgi_view_launch_shade_proj(const ShadeProjArgs &a, int projection, hipStream_t s);
+hipError_t fmgi_view_launch_trace_proj(const TraceProjArgs &t, int projection, hipStream_t s);
+
 hipError_t fmgi_view_launch_trace(const TraceArgs &t, hipStream_t s);
 hipError_t fmgi_view_launch_resolve(const ResolveArgs &r, hipStream_t s);
 

@@ -3,7 +3,8 @@
  * (debugRaytracer.cc:121-176 over radiosityNative.c:25-90); see fmgi_view.h for the kernel plan.
  *
  * Arithmetic: IEEE fp32 in the reference's source order (gcc -O2 -msse3, no FMA), contraction off, with
- * the helpers the radiosity backend uses (fmgi_rect_dev.h).
+ * the helpers the radiosity backend uses (fmgi_rect_dev.h). The orthographic and equirectangular cameras
+ * (no reference program) are the _proj instances; they call the pin-hole kernels' device functions.
  */
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 
 #pragma clang fp contract(off)
 
+#include "fmgi_math.h"
 #include "fmgi_rect_dev.h"
 
 namespace {
@@ -249,6 +251,178 @@ __global__ __launch_bounds__(256) void k_view_shade(ShadeArgs s) {
     if (lane == 0 && n) atomicAdd(a.tests, n);
 }
 
+/*
+ * The orthographic and equirectangular cameras. The host puts the orthonormal frame into the
+ * ViewCam: d = f, r = normalized(cross(f, up)), u = cross(r, f), c = pos + f.
+ *
+ * The candidate lists of the two projections, k_view_candidates' sort and output:
+ *   ORTHO     walls that face against f and have a corner at depth >= 0 along f; the key is the smallest
+ *             corner depth, clamped to 0 from below (every ray of the camera has direction f, so a hit's
+ *             distance is a depth between its wall's corner depths);
+ *   EQUIRECT  the pin-hole's list without isBehindRay: the rays leave the camera in every direction.
+ */
+template <int P>
+__global__ __launch_bounds__(256) void k_view_candidates_proj(ViewArgs a) {
+    extern __shared__ unsigned long long keys[];
+    __shared__ int ncand;
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x;
+    const ViewCam V = a.cams[c];
+    const v3 cam = mk(V.px, V.py, V.pz), f = mk(V.dx, V.dy, V.dz);
+    if (tid == 0) ncand = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = tid; i < a.sort_n; i += blockDim.x) {
+        unsigned long long key = ~0ull;
+        if (i < a.nrects) {
+            const RadRect r = a.rects[i];
+            const v3 pos = mk(r.px, r.py, r.pz), w = mk(r.wx, r.wy, r.wz), h = mk(r.hx, r.hy, r.hz),
+                     rn = mk(r.nx, r.ny, r.nz);
+            bool keep;
+            float md;
+            if constexpr (P == FMGI_VIEW_ORTHO) {
+                /* the corners in behind_ray's order */
+                const float e1 = dot(sub(pos, cam), f), e2 = dot(sub(add(pos, w), cam), f),
+                            e3 = dot(sub(add(pos, h), cam), f), e4 = dot(sub(add(add(pos, w), h), cam), f);
+                const float m12 = e1 < e2 ? e1 : e2, m34 = e3 < e4 ? e3 : e4, m = m12 < m34 ? m12 : m34;
+                keep = dot(rn, f) < 0 && !(e1 < 0 && e2 < 0 && e3 < 0 && e4 < 0);
+                md = m < 0 ? 0.0f : m;
+            } else {
+                keep = !(dot(rn, sub(pos, cam)) > 0);
+                md = keep ? min_dist(pos, w, h, rn, cam) : 0.0f;
+            }
+            if (keep) {
+                key = ((unsigned long long)__float_as_uint(md) << 32) | (uint32_t)i;
+                mine++;
+            }
+        }
+        keys[i] = key;
+    }
+    if (mine) atomicAdd(&ncand, mine);
+    __syncthreads();
+    /* bitonic sort, ascending */
+    for (int k = 2; k <= a.sort_n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < a.sort_n / 2; i += blockDim.x) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
+                const unsigned long long x = keys[lo], y = keys[hi];
+                if ((x > y) == ((lo & k) == 0)) {
+                    keys[lo] = y;
+                    keys[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    unsigned long long *out = a.keys + (size_t)c * a.sort_n;
+    for (int i = tid; i < a.sort_n; i += blockDim.x) out[i] = keys[i];
+    if (tid == 0) a.counts[c] = ncand;
+}
+
+/* ORTHO: the origin of the ray through the screen point (fx, fy) */
+__device__ __forceinline__ v3 ortho_origin(const ViewCam &V, v3 cam, float fx, float fy) {
+    return add(add(cam, mul(mk(V.rx, V.ry, V.rz), fx)), mul(mk(V.ux, V.uy, V.uz), fy));
+}
+
+/* EQUIRECT: the ray of longitude phi (sp, cp) and polar angle theta (st, ct): column width / 2 looks along f,
+   x grows to the right, row 0 is straight up */
+__device__ __forceinline__ v3 equirect_dir(const ViewCam &V, float sp, float cp, float st, float ct) {
+    const float ea = (-cp) * st, eb = (-sp) * st;
+    return unit(add(add(mul(mk(V.dx, V.dy, V.dz), ea), mul(mk(V.rx, V.ry, V.rz), eb)), mul(mk(V.ux, V.uy, V.uz), ct)));
+}
+
+/* EQUIRECT: the sines and cosines of a column's sample longitudes, once per lane. A lane keeps its S pairs in
+   its own LDS slots ([sample][lane], 16 KB per workgroup, no bank conflicts, no barrier: nobody else reads
+   them); registers indexed by the sample loop would cost the kernel half its occupancy. */
+struct PhiTable {
+    float2 sc[FMGI_VIEW_SAMPLES][256];
+};
+__device__ __forceinline__ void phi_table(PhiTable &t, int tid, int x, int S, const float *offs, float kphi) {
+    for (int i = 0; i < S; i++) {
+        float sn, cs;
+        fmgi_sincosf(((float)x + (0.5f + offs[i])) * kphi, &sn, &cs);
+        t.sc[i][tid] = make_float2(sn, cs);
+    }
+}
+
+/*
+ * k_view_shade for the two projections: the same pixel mapping, sample loop, walk, taps and fixed-point resolve;
+ * only the sample's ray differs. ORTHO moves the origin over the screen plane and keeps the direction f;
+ * EQUIRECT keeps the origin and takes theta's sine and cosine once per sample row, phi's once per lane and column.
+ */
+template <int P>
+__global__ __launch_bounds__(256) void k_view_shade_proj(ShadeProjArgs q) {
+    const ShadeArgs &s = q.s;
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    __shared__ PhiTable phis; /* EQUIRECT only; ORTHO never touches it and the compiler drops it */
+    unsigned long long tests = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz), f = mk(V.dx, V.dy, V.dz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool colour = a.rgb_out != nullptr, bilinear = s.filter != 0;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        const int bg0 = fix8((float)(a.background & 255)), bg1 = fix8((float)((a.background >> 8) & 255)),
+                  bg2 = fix8((float)((a.background >> 16) & 255));
+        if constexpr (P == FMGI_VIEW_EQUIRECT) phi_table(phis, tid, x, S, s.offs, q.kphi);
+        int sum0 = 0, sum1 = 0, sum2 = 0, cov = 0;
+        for (int j = 0; j < S; j++) {
+            float fy = 0.0f, st = 0.0f, ct = 0.0f;
+            if constexpr (P == FMGI_VIEW_ORTHO) fy = -V.pixel * (py + s.offs[j]);
+            else fmgi_sincosf(((float)y + (0.5f + s.offs[j])) * q.ktheta, &st, &ct);
+            for (int i = 0; i < S; i++) {
+                v3 src = cam, dir = f;
+                if constexpr (P == FMGI_VIEW_ORTHO) src = ortho_origin(V, cam, V.pixel * (px + s.offs[i]), fy);
+                else dir = equirect_dir(V, phis.sc[i][tid].x, phis.sc[i][tid].y, st, ct);
+                float dist;
+                const int target = view_walk(a, keys, C, src, dir, dist, tests);
+                if (target < 0) {
+                    sum0 += bg0, sum1 += bg1, sum2 += bg2;
+                    continue;
+                }
+                cov++;
+                if (!colour) continue;
+                const RadRect tr = a.rects[target];
+                float u, v;
+                view_uv(a.hits[target], tr, src, dir, dist, u, v);
+                const uint32_t *T = s.tiles + a.first_tile[target];
+                if (!bilinear) {
+                    const uint32_t w = T[clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1)];
+                    sum0 += fix8((float)(w & 255)), sum1 += fix8((float)((w >> 8) & 255)), sum2 += fix8((float)((w >> 16) & 255));
+                    continue;
+                }
+                int xa, xb, ya, yb;
+                float fu, fv;
+                tap_axis(u, tr.s1, xa, xb, fu);
+                tap_axis(v, tr.s2, ya, yb, fv);
+                const uint32_t w00 = T[ya * tr.s1 + xa], w01 = T[ya * tr.s1 + xb], w10 = T[yb * tr.s1 + xa],
+                               w11 = T[yb * tr.s1 + xb];
+#define FMGI_CH(sh)                                                                                        \
+    fix8(lerp2(fv, lerp2(fu, (float)((w00 >> sh) & 255), (float)((w01 >> sh) & 255)),                    \
+               lerp2(fu, (float)((w10 >> sh) & 255), (float)((w11 >> sh) & 255))))
+                sum0 += FMGI_CH(0), sum1 += FMGI_CH(8), sum2 += FMGI_CH(16);
+#undef FMGI_CH
+            }
+        }
+        const int64_t o = ((int64_t)c * a.height + y) * a.width + x;
+        if (colour) {
+            const int half = 128 * S * S, den = 256 * S * S;
+            uint8_t *p = a.rgb_out + 3 * o;
+            p[0] = (uint8_t)((sum0 + half) / den);
+            p[1] = (uint8_t)((sum1 + half) / den);
+            p[2] = (uint8_t)((sum2 + half) / den);
+        }
+        if (s.cov_out) s.cov_out[o] = (uint8_t)cov;
+    }
+    const unsigned long long n = wave_sum(tests);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
+}
+
 /* sample n of camera c, pixel (y, x): its record's index in [c][n][y][x] */
 __device__ __forceinline__ int64_t record_index(int c, int spp, int n, int height, int width, int y, int x) {
     return (((int64_t)c * spp + n) * height + y) * width + x;
@@ -288,6 +462,67 @@ __global__ __launch_bounds__(256) void k_view_trace(TraceArgs t) {
                     const RadRect tr = a.rects[target];
                     float u, v;
                     view_uv(a.hits[target], tr, cam, dir, dist, u, v);
+                    const uint32_t first = (uint32_t)a.first_tile[target];
+                    if (!bilinear) {
+                        rec.x = first + (uint32_t)(clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1));
+                    } else {
+                        int xa, xb, ya, yb;
+                        float fu, fv;
+                        tap_axis(u, tr.s1, xa, xb, fu);
+                        tap_axis(v, tr.s2, ya, yb, fv);
+                        rec.x = (first + (uint32_t)(ya * tr.s1 + xa)) | ((uint32_t)(xb != xa) << 31);
+                        rec.y = first + (uint32_t)(yb * tr.s1 + xa);
+                        rec.z = __float_as_uint(fu);
+                        rec.w = __float_as_uint(fv);
+                    }
+                }
+                if (bilinear) ((uint4 *)t.records)[o] = rec;
+                else ((uint32_t *)t.records)[o] = rec.x;
+            }
+        }
+    }
+    const unsigned long long n = wave_sum(tests), h = wave_sum(hits);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
+    if (lane == 0 && h) atomicAdd(t.hits, h);
+}
+
+/* k_view_trace for the two projections: k_view_shade_proj's rays, k_view_trace's records */
+template <int P>
+__global__ __launch_bounds__(256) void k_view_trace_proj(TraceProjArgs q) {
+    const TraceArgs &t = q.t;
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    __shared__ PhiTable phis; /* EQUIRECT only */
+    unsigned long long tests = 0, hits = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz), f = mk(V.dx, V.dy, V.dz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool bilinear = s.filter != 0;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        if constexpr (P == FMGI_VIEW_EQUIRECT) phi_table(phis, tid, x, S, s.offs, q.kphi);
+        for (int j = 0; j < S; j++) {
+            float fy = 0.0f, st = 0.0f, ct = 0.0f;
+            if constexpr (P == FMGI_VIEW_ORTHO) fy = -V.pixel * (py + s.offs[j]);
+            else fmgi_sincosf(((float)y + (0.5f + s.offs[j])) * q.ktheta, &st, &ct);
+            for (int i = 0; i < S; i++) {
+                v3 src = cam, dir = f;
+                if constexpr (P == FMGI_VIEW_ORTHO) src = ortho_origin(V, cam, V.pixel * (px + s.offs[i]), fy);
+                else dir = equirect_dir(V, phis.sc[i][tid].x, phis.sc[i][tid].y, st, ct);
+                float dist;
+                const int target = view_walk(a, keys, C, src, dir, dist, tests);
+                const int64_t o = record_index(c, S * S, j * S + i, a.height, a.width, y, x);
+                uint4 rec = make_uint4(FMGI_VIEW_MISS, 0u, 0u, 0u);
+                if (target >= 0) {
+                    hits++;
+                    const RadRect tr = a.rects[target];
+                    float u, v;
+                    view_uv(a.hits[target], tr, src, dir, dist, u, v);
                     const uint32_t first = (uint32_t)a.first_tile[target];
                     if (!bilinear) {
                         rec.x = first + (uint32_t)(clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1));
@@ -445,6 +680,60 @@ hipError_t fmgi_view_launch_trace(const TraceArgs &t, hipStream_t st) {
     const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
                     (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
     hipLaunchKernelGGL(k_view_trace, grid, dim3(256), 0, st, t);
+    return hipGetLastError();
+}
+
+static bool bad_proj(int projection) { return projection != FMGI_VIEW_ORTHO && projection != FMGI_VIEW_EQUIRECT; }
+
+hipError_t fmgi_view_launch_candidates_proj(const ViewArgs &a, int projection, hipStream_t s) {
+    if (bad_proj(projection)) return hipErrorInvalidValue;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.sort_n * 8;
+    if (projection == FMGI_VIEW_ORTHO) {
+        hipError_t e = fmgi_set_lds_attr_once<8>((const void *)k_view_candidates_proj<FMGI_VIEW_ORTHO>, FMGI_RAD_MAX_SORT * 8);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_view_candidates_proj<FMGI_VIEW_ORTHO>, dim3((unsigned)a.ncams), dim3(256), lds, s, a);
+    } else {
+        hipError_t e = fmgi_set_lds_attr_once<9>((const void *)k_view_candidates_proj<FMGI_VIEW_EQUIRECT>, FMGI_RAD_MAX_SORT * 8);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_view_candidates_proj<FMGI_VIEW_EQUIRECT>, dim3((unsigned)a.ncams), dim3(256), lds, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_shade_proj(const ShadeProjArgs &q, int projection, hipStream_t st) {
+    const ShadeArgs &s = q.s;
+    const ViewArgs &a = s.v;
+    if (bad_proj(projection)) return hipErrorInvalidValue;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a) || a.ncams > FMGI_VIEW_MAX_BATCH || a.width < 1 || a.height < 1 ||
+        a.width > FMGI_VIEW_MAX_DIM || a.height > FMGI_VIEW_MAX_DIM || (a.rgb_out && (!s.tiles || !a.first_tile)) ||
+        s.samples < 1 || s.samples > FMGI_VIEW_SAMPLES || (s.filter != 0 && s.filter != 1) || s.x0 < 0 || s.y0 < 0 ||
+        s.x1 <= s.x0 || s.y1 <= s.y0 || s.x1 > a.width || s.y1 > a.height)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    if (projection == FMGI_VIEW_ORTHO) hipLaunchKernelGGL(k_view_shade_proj<FMGI_VIEW_ORTHO>, grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(k_view_shade_proj<FMGI_VIEW_EQUIRECT>, grid, dim3(256), 0, st, q);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_trace_proj(const TraceProjArgs &q, int projection, hipStream_t st) {
+    const TraceArgs &t = q.t;
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    if (bad_proj(projection)) return hipErrorInvalidValue;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a) || a.ncams > FMGI_VIEW_MAX_BATCH || a.width < 1 || a.height < 1 ||
+        a.width > FMGI_VIEW_MAX_DIM || a.height > FMGI_VIEW_MAX_DIM || !a.first_tile || !t.records || !t.hits ||
+        s.samples < 1 || s.samples > FMGI_VIEW_SAMPLES || (s.filter != 0 && s.filter != 1) || s.x0 < 0 || s.y0 < 0 ||
+        s.x1 <= s.x0 || s.y1 <= s.y0 || s.x1 > a.width || s.y1 > a.height)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    if (projection == FMGI_VIEW_ORTHO) hipLaunchKernelGGL(k_view_trace_proj<FMGI_VIEW_ORTHO>, grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(k_view_trace_proj<FMGI_VIEW_EQUIRECT>, grid, dim3(256), 0, st, q);
     return hipGetLastError();
 }
 

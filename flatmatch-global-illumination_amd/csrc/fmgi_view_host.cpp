@@ -10,7 +10,9 @@
  * requested outputs back. fmgi_shade_views (supersampled, filtered views; no reference program) takes the same
  * path into k_view_shade, in launches of a bounded number of rays. fmgi_view_cache_* (traced views)
  * casts the same rays once with k_view_trace and shades device-resident lightmaps with k_output's read-only form
- * and k_view_resolve, asynchronously on the caller's stream.
+ * and k_view_resolve, asynchronously on the caller's stream. The *_proj entry points pass a projection
+ * through the same functions: the pin-hole takes the calls above unchanged, the orthographic and equirectangular
+ * cameras get an orthonormal frame in their ViewCam and the _proj instances of the three kernels.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -96,8 +98,8 @@ int check_geometry(const fmgi_geometry *geo, Walls &w, const char *fn) {
 }
 
 /* debugRaytracer.cc:121-125 */
-int make_cam(const fmgi_camera &c, ViewCam &o, const char *fn) {
-    if (!(c.pixel > 0) || !isfinite(c.pixel))
+int make_cam(const fmgi_camera &c, ViewCam &o, const char *fn, bool reads_pixel = true) {
+    if (reads_pixel && (!(c.pixel > 0) || !isfinite(c.pixel)))
         return arg_err(fn, "a camera's pixel size is not finite and positive");
     const F3 pos{c.pos[0], c.pos[1], c.pos[2]}, d{c.dir[0], c.dir[1], c.dir[2]}, up{c.up[0], c.up[1], c.up[2]};
     const float len = length(d);
@@ -111,7 +113,33 @@ int make_cam(const fmgi_camera &c, ViewCam &o, const char *fn) {
     o.cx = centre.x, o.cy = centre.y, o.cz = centre.z;
     o.rx = right.x, o.ry = right.y, o.rz = right.z;
     o.ux = up.x, o.uy = up.y, o.uz = up.z;
-    o.pixel = c.pixel;
+    o.pixel = reads_pixel ? c.pixel : 0.0f;
+    return FMGI_OK;
+}
+
+static_assert(FMGI_VIEW_PINHOLE == FMGI_PROJ_PINHOLE && FMGI_VIEW_ORTHO == FMGI_PROJ_ORTHO &&
+                  FMGI_VIEW_EQUIRECT == FMGI_PROJ_EQUIRECT, "kernel and ABI projections differ");
+
+/* a call's cameras: make_cam's checks for every camera (EQUIRECT does not read the pixel size), then the
+   projection, then, for ORTHO and EQUIRECT, the orthonormal frame: r = normalized(cross(f, up)),
+   u = cross(r, f) */
+int make_cams(const fmgi_camera *cams, int n, int projection, std::vector<ViewCam> &vc, const char *fn) {
+    int rc;
+    for (int i = 0; i < n; i++)
+        if ((rc = make_cam(cams[i], vc[(size_t)i], fn, projection != FMGI_PROJ_EQUIRECT)) != FMGI_OK) return rc;
+    if (projection == FMGI_PROJ_PINHOLE) return FMGI_OK;
+    if (projection != FMGI_PROJ_ORTHO && projection != FMGI_PROJ_EQUIRECT)
+        return arg_err(fn, "projection is none of pinhole, ortho and equirect");
+    for (int i = 0; i < n; i++) {
+        ViewCam &o = vc[(size_t)i];
+        const F3 f{o.dx, o.dy, o.dz}, r0{o.rx, o.ry, o.rz}; /* make_cam's cross(f, up) */
+        const float len = length(r0);
+        if (!(len > 0) || !isfinite(len) || !isfinite(1.0f / len))
+            return arg_err(fn, "a camera's up vector is parallel to its direction: cross(dir, up) has no length");
+        const F3 r = normalized(r0), u = cross(r, f);
+        o.rx = r.x, o.ry = r.y, o.rz = r.z;
+        o.ux = u.x, o.uy = u.y, o.uz = u.z;
+    }
     return FMGI_OK;
 }
 
@@ -248,13 +276,15 @@ done:
     return rc;
 }
 
-int candidates_run(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist, int cap) {
+int candidates_run(const fmgi_geometry *geo, const fmgi_camera *cam, int projection, int32_t *wall_idx,
+                   float *min_dist, int cap) {
     Walls w;
     int rc = check_geometry(geo, w, "fmgi_view_candidates");
     if (rc != FMGI_OK) return rc;
     if (!cam) return internal_set_err(FMGI_ERR_ARG, "fmgi_view_candidates: null camera");
-    ViewCam vc;
-    if ((rc = make_cam(*cam, vc, "fmgi_view_candidates")) != FMGI_OK) return rc;
+    std::vector<ViewCam> one(1);
+    if ((rc = make_cams(cam, 1, projection, one, "fmgi_view_candidates")) != FMGI_OK) return rc;
+    const ViewCam vc = one[0];
     if ((rc = no_device()) != FMGI_OK) return rc;
     RadRect *d_rects = nullptr;
     ViewCam *d_cams = nullptr;
@@ -281,7 +311,8 @@ int candidates_run(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wa
     a.ncams = 1;
     a.keys = d_keys;
     a.counts = d_counts;
-    VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    else VIEWCHK(fmgi_view_launch_candidates_proj(a, projection, nullptr));
     VIEWCHK(hipMemcpy(keys.data(), d_keys, keys.size() * 8, hipMemcpyDeviceToHost));
     VIEWCHK(hipMemcpy(&count, d_counts, 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < std::min(count, std::max(cap, 0)); i++) {
@@ -317,7 +348,7 @@ int64_t shade_ray_budget() {
 }
 
 int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
-              const uint8_t *tiles_rgb, const uint8_t *background, int samples, int filter, uint8_t *rgb_out,
+              int projection, const uint8_t *tiles_rgb, const uint8_t *background, int samples, int filter, uint8_t *rgb_out,
               uint8_t *coverage_out) {
     static const char fn[] = "fmgi_shade_views";
     Walls w;
@@ -330,8 +361,7 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
     if (samples < 1 || samples > FMGI_VIEW_MAX_SAMPLES) return arg_err(fn, "samples outside 1..8");
     if (filter != FMGI_VIEW_NEAREST && filter != FMGI_VIEW_BILINEAR) return arg_err(fn, "filter is neither nearest nor bilinear");
     std::vector<ViewCam> vc((size_t)std::max(num_cams, 1));
-    for (int i = 0; i < num_cams; i++)
-        if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
+    if ((rc = make_cams(cams, num_cams, projection, vc, fn)) != FMGI_OK) return rc;
     memset(&g_stats, 0, sizeof g_stats);
     if (num_cams == 0) return FMGI_OK;
     if ((rc = no_device()) != FMGI_OK) return rc;
@@ -353,9 +383,12 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<int32_t> counts((size_t)batch);
     unsigned long long tests = 0;
-    ShadeArgs s;
-    memset(&s, 0, sizeof s);
+    ShadeProjArgs q;
+    memset(&q, 0, sizeof q);
+    ShadeArgs &s = q.s;
     ViewArgs &a = s.v;
+    q.kphi = 6.2831855f / (float)width;
+    q.ktheta = 3.1415927f / (float)height;
     {
         const char *dv = getenv("FMGI_DEVICE");
         VIEWCHK(hipSetDevice(dv ? atoi(dv) : 0));
@@ -408,13 +441,15 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
         a.ncams = n;
         VIEWCHK(hipMemcpy(d_cams.p, vc.data() + c0, (size_t)n * sizeof(ViewCam), hipMemcpyHostToDevice));
         VIEWCHK(hipEventRecord(ev[1], nullptr));
-        VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+        if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+        else VIEWCHK(fmgi_view_launch_candidates_proj(a, projection, nullptr));
         VIEWCHK(hipEventRecord(ev[2], nullptr));
         for (s.y0 = 0; s.y0 < height; s.y0 += rows)
             for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
                 s.y1 = std::min(height, s.y0 + rows);
                 s.x1 = std::min(width, s.x0 + cols);
-                VIEWCHK(fmgi_view_launch_shade(s, nullptr));
+                if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_shade(s, nullptr));
+                else VIEWCHK(fmgi_view_launch_shade_proj(q, projection, nullptr));
             }
         VIEWCHK(hipEventRecord(ev[3], nullptr));
         VIEWCHK(hipEventSynchronize(ev[3]));
@@ -449,6 +484,7 @@ done:
  */
 struct fmgi_view_cache {
     int device = 0;
+    int projection = FMGI_PROJ_PINHOLE;
     struct fmgi_view_cache_info info;
     std::vector<OutWallIn> walls; /* what the OutWall table is made of; norm follows the call's spa */
     DevBuf records, out_walls, packed;
@@ -479,8 +515,8 @@ int64_t cache_bytes(int num_cams, int width, int height, int samples, int filter
     return (int64_t)num_cams * width * height * samples * samples * (filter == FMGI_VIEW_BILINEAR ? 16 : 4);
 }
 
-int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height, int samples,
-                 int filter, fmgi_view_cache **out) {
+int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height, int projection,
+                 int samples, int filter, fmgi_view_cache **out) {
     static const char fn[] = "fmgi_view_cache_create";
     if (!out) return arg_err(fn, "null out");
     *out = nullptr;
@@ -490,8 +526,7 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     if (const char *msg = cache_shape_error(num_cams, cams != nullptr, width, height, samples, filter))
         return arg_err(fn, msg);
     std::vector<ViewCam> vc((size_t)num_cams);
-    for (int i = 0; i < num_cams; i++)
-        if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
+    if ((rc = make_cams(cams, num_cams, projection, vc, fn)) != FMGI_OK) return rc;
     const int nr = geo->numWalls;
     std::vector<OutWallIn> ow((size_t)nr);
     int64_t ntiles = 0;
@@ -517,10 +552,14 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     unsigned long long counters[2] = {0, 0};
     float ms = 0;
-    TraceArgs t;
-    memset(&t, 0, sizeof t);
+    TraceProjArgs q;
+    memset(&q, 0, sizeof q);
+    TraceArgs &t = q.t;
     ShadeArgs &s = t.s;
     ViewArgs &a = s.v;
+    q.kphi = 6.2831855f / (float)width;
+    q.ktheta = 3.1415927f / (float)height;
+    v->projection = projection;
     {
         const char *dv = getenv("FMGI_DEVICE");
         v->device = dv ? atoi(dv) : 0;
@@ -567,7 +606,8 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     a.counts = d_counts.as<int32_t>();
     a.ncams = num_cams;
     VIEWCHK(hipEventRecord(ev[0], nullptr));
-    VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
+    else VIEWCHK(fmgi_view_launch_candidates_proj(a, projection, nullptr));
     VIEWCHK(hipEventRecord(ev[1], nullptr));
     for (int c0 = 0; c0 < num_cams; c0 += batch) {
         a.ncams = std::min(batch, num_cams - c0);
@@ -579,7 +619,8 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
             for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
                 s.y1 = std::min(height, s.y0 + rows);
                 s.x1 = std::min(width, s.x0 + cols);
-                VIEWCHK(fmgi_view_launch_trace(t, nullptr));
+                if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_trace(t, nullptr));
+                else VIEWCHK(fmgi_view_launch_trace_proj(q, projection, nullptr));
             }
     }
     VIEWCHK(hipEventRecord(ev[2], nullptr));
@@ -701,7 +742,17 @@ FMGI_API int64_t fmgi_view_cache_bytes(int num_cams, int width, int height, int 
 
 FMGI_API int fmgi_view_cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
                                     int height, int samples, int filter, fmgi_view_cache **out) {
-    return cache_create(geo, cams, num_cams, width, height, samples, filter, out);
+    return cache_create(geo, cams, num_cams, width, height, FMGI_PROJ_PINHOLE, samples, filter, out);
+}
+
+FMGI_API int fmgi_view_cache_create_proj(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
+                                         int height, int projection, int samples, int filter, fmgi_view_cache **out) {
+    return cache_create(geo, cams, num_cams, width, height, projection, samples, filter, out);
+}
+
+FMGI_API int fmgi_view_cache_projection(const fmgi_view_cache *vc) {
+    if (!vc) return arg_err("fmgi_view_cache_projection", "null argument");
+    return vc->projection;
 }
 
 FMGI_API void fmgi_view_cache_destroy(fmgi_view_cache *vc) {
@@ -733,7 +784,15 @@ FMGI_API int fmgi_view_cache_shade(const fmgi_view_cache *vc, const void *const 
 FMGI_API int fmgi_shade_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
                               const uint8_t *tiles_rgb, const uint8_t background[3], int samples, int filter,
                               uint8_t *rgb_out, uint8_t *coverage_out) {
-    return shade_run(geo, cams, num_cams, width, height, tiles_rgb, background, samples, filter, rgb_out, coverage_out);
+    return shade_run(geo, cams, num_cams, width, height, FMGI_PROJ_PINHOLE, tiles_rgb, background, samples, filter, rgb_out,
+                     coverage_out);
+}
+
+FMGI_API int fmgi_shade_views_proj(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                                   int projection, const uint8_t *tiles_rgb, const uint8_t background[3], int samples,
+                                   int filter, uint8_t *rgb_out, uint8_t *coverage_out) {
+    return shade_run(geo, cams, num_cams, width, height, projection, tiles_rgb, background, samples, filter, rgb_out,
+                     coverage_out);
 }
 
 FMGI_API int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
@@ -744,7 +803,12 @@ FMGI_API int fmgi_render_views(const fmgi_geometry *geo, const fmgi_camera *cams
 
 FMGI_API int fmgi_view_candidates(const fmgi_geometry *geo, const fmgi_camera *cam, int32_t *wall_idx, float *min_dist,
                                   int cap) {
-    return candidates_run(geo, cam, wall_idx, min_dist, cap);
+    return candidates_run(geo, cam, FMGI_PROJ_PINHOLE, wall_idx, min_dist, cap);
+}
+
+FMGI_API int fmgi_view_candidates_proj(const fmgi_geometry *geo, const fmgi_camera *cam, int projection,
+                                       int32_t *wall_idx, float *min_dist, int cap) {
+    return candidates_run(geo, cam, projection, wall_idx, min_dist, cap);
 }
 
 FMGI_API int fmgi_view_stats(struct fmgi_view_stats *out) {

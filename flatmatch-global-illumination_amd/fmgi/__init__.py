@@ -24,6 +24,7 @@ from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
                    SPARSE_COUNT_BITS, SparseInfo, BakeSparseStats,
                    VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewStats, check,
+                   PROJ_EQUIRECT, PROJ_ORTHO, PROJ_PINHOLE,
                    RAD_CACHE_MAX_ITERATIONS, RAD_CACHE_MAX_SETS, RadCacheInfo,
                    load)
 from .scene import RECT_DTYPE, Scene
@@ -67,6 +68,7 @@ __all__ = [
     "ViewCache",
     "view_cache_bytes",
     "VIEW_CACHE_MAX_SETS",
+    "PROJECTIONS",
     "RadCache",
     "rad_cache_bytes",
     "rad_reference_emit",
@@ -911,18 +913,28 @@ def render_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray
 
 
 _VIEW_FILTERS = {"nearest": VIEW_NEAREST, "bilinear": VIEW_BILINEAR}
+PROJECTIONS = {"pinhole": PROJ_PINHOLE, "ortho": PROJ_ORTHO, "equirect": PROJ_EQUIRECT}
+
+
+def _projection(projection) -> int:
+    if projection not in PROJECTIONS:
+        raise FmgiError(f"projection {projection!r}: one of {sorted(PROJECTIONS)}")
+    return PROJECTIONS[projection]
 
 
 def shade_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray | None = None, background=(0, 0, 0),
-                samples: int = 1, filter: str = "nearest") -> dict:
+                samples: int = 1, filter: str = "nearest", *, projection: str = "pinhole") -> dict:
     """Supersampled, filtered camera views (fmgi_shade_views): samples x samples rays per pixel, each coloured
     from the hit wall's tiles ("nearest": the tile it lands in, "bilinear": the four around it, clamped to the
     wall) or `background`, averaged in fixed point. Returns {"coverage"} (uint8 [cameras, height, width]: the
     pixel's rays that hit a wall) and, when tiles_rgb is given, {"rgb"} (uint8, a trailing [3]). samples=1 with
-    "nearest" gives render_views' rgb."""
+    "nearest" gives render_views' rgb. projection: "pinhole", "ortho" (parallel rays along dir, `pixel` metres
+    per pixel: the plan at true scale) or "equirect" (the 360-degree panorama from pos, column width / 2 looking
+    along dir; fmgi_shade_views_proj)."""
     lib = load()
     if filter not in _VIEW_FILTERS:
         raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
+    proj = _projection(projection)
     cams = _cameras(cams)
     n = len(cams)
     g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
@@ -935,25 +947,37 @@ def shade_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray 
     bg = np.array(background, np.uint8)
     assert bg.shape == (3,)
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    check(lib.fmgi_shade_views(C.byref(g), p(cams), n, width, height, None if tiles is None else p(tiles), p(bg),
-                               samples, _VIEW_FILTERS[filter], p(out["rgb"]) if tiles is not None else None,
-                               p(out["coverage"])), "fmgi_shade_views")
+    if proj == PROJ_PINHOLE:
+        check(lib.fmgi_shade_views(C.byref(g), p(cams), n, width, height, None if tiles is None else p(tiles), p(bg),
+                                   samples, _VIEW_FILTERS[filter], p(out["rgb"]) if tiles is not None else None,
+                                   p(out["coverage"])), "fmgi_shade_views")
+    else:
+        check(lib.fmgi_shade_views_proj(C.byref(g), p(cams), n, width, height, proj,
+                                        None if tiles is None else p(tiles), p(bg), samples, _VIEW_FILTERS[filter],
+                                        p(out["rgb"]) if tiles is not None else None, p(out["coverage"])),
+              "fmgi_shade_views_proj")
     del keep
     return out
 
 
-def view_candidates(sc: Scene, cam):
+def view_candidates(sc: Scene, cam, *, projection: str = "pinhole"):
     """One camera's sorted candidate list from the device (fmgi_view_candidates): (wall indices int32,
-    minDistance float32), in the order the rays walk it."""
+    minDistance float32), in the order the rays walk it. projection "ortho" / "equirect": that camera's list
+    (fmgi_view_candidates_proj); "ortho" keys are depths along dir."""
     lib = load()
+    proj = _projection(projection)
     cams = _cameras(cam)
     assert len(cams) == 1
     g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
     cap = len(sc.walls)
     idx = np.zeros(max(cap, 1), np.int32)
     md = np.zeros(max(cap, 1), np.float32)
-    n = check(lib.fmgi_view_candidates(C.byref(g), cams.ctypes.data_as(C.c_void_p), _ptr(idx), _ptr(md), cap),
-              "fmgi_view_candidates")
+    if proj == PROJ_PINHOLE:
+        n = check(lib.fmgi_view_candidates(C.byref(g), cams.ctypes.data_as(C.c_void_p), _ptr(idx), _ptr(md), cap),
+                  "fmgi_view_candidates")
+    else:
+        n = check(lib.fmgi_view_candidates_proj(C.byref(g), cams.ctypes.data_as(C.c_void_p), proj, _ptr(idx), _ptr(md),
+                                                cap), "fmgi_view_candidates_proj")
     del keep
     return idx[:n], md[:n]
 
@@ -984,18 +1008,31 @@ class ViewCache:
     tiles() runs the output step on device lightmaps and shade() gathers one picture per tile set, each what
     output_tiles followed by shade_views gives, with no host round trip. Device buffers are integer addresses."""
 
-    def __init__(self, sc: Scene, cams, width: int, height: int, samples: int = 1, filter: str = "nearest"):
+    def __init__(self, sc: Scene, cams, width: int, height: int, samples: int = 1, filter: str = "nearest", *,
+                 projection: str = "pinhole"):
         self.lib = load()
         self.h = None
         if filter not in _VIEW_FILTERS:
             raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
+        proj = _projection(projection)
         cams = _cameras(cams)
         g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
         h = C.c_void_p()
-        check(self.lib.fmgi_view_cache_create(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width, height,
-                                              samples, _VIEW_FILTERS[filter], C.byref(h)), "fmgi_view_cache_create")
+        if proj == PROJ_PINHOLE:
+            check(self.lib.fmgi_view_cache_create(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width, height,
+                                                  samples, _VIEW_FILTERS[filter], C.byref(h)), "fmgi_view_cache_create")
+        else:
+            check(self.lib.fmgi_view_cache_create_proj(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width,
+                                                       height, proj, samples, _VIEW_FILTERS[filter], C.byref(h)),
+                  "fmgi_view_cache_create_proj")
         del keep
         self.h = h
+
+    @property
+    def projection(self) -> str:
+        """the camera model the view was traced with: "pinhole", "ortho" or "equirect" """
+        code = check(self.lib.fmgi_view_cache_projection(self.h), "fmgi_view_cache_projection")
+        return {v: k for k, v in PROJECTIONS.items()}[code]
 
     def close(self):
         if self.h:

@@ -83,6 +83,10 @@ EXPORTS = (
     "fmgi_view_cache_info",
     "fmgi_view_cache_tiles",
     "fmgi_view_cache_shade",
+    "fmgi_shade_views_proj",
+    "fmgi_view_candidates_proj",
+    "fmgi_view_cache_create_proj",
+    "fmgi_view_cache_projection",
     "fmgi_palette_reference",
     "fmgi_palette_table",
     "fmgi_states_bytes",
@@ -120,6 +124,9 @@ VIEW_NEAREST = 0
 VIEW_BILINEAR = 1
 VIEW_MAX_SAMPLES = 8
 VIEW_CACHE_MAX_SETS = 8
+PROJ_PINHOLE = 0
+PROJ_ORTHO = 1
+PROJ_EQUIRECT = 2
 RAD_CACHE_MAX_SETS = 8
 RAD_CACHE_MAX_ITERATIONS = 64
 COLOUR_STATE_COUNT = 1024
@@ -430,6 +437,11 @@ def load() -> C.CDLL:
         "fmgi_view_cache_info": (C.c_int, [vp, C.POINTER(ViewCacheInfo)]),
         "fmgi_view_cache_tiles": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
         "fmgi_view_cache_shade": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
+        "fmgi_shade_views_proj": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+        "fmgi_view_candidates_proj": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int]),
+        "fmgi_view_cache_create_proj": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(vp)]),
+        "fmgi_view_cache_projection": (C.c_int, [vp]),
         "fmgi_palette_reference": (None, [C.POINTER(Palette)]),
         "fmgi_palette_table": (C.c_int, [C.POINTER(Palette), vp]),
         "fmgi_states_bytes": (C.c_size_t, [C.c_int]),

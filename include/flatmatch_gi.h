@@ -283,6 +283,34 @@ int  fmgi_view_cache_tiles(const fmgi_view_cache *vc, const void *const *texels_
 int  fmgi_view_cache_shade(const fmgi_view_cache *vc, const void *const *tiles_dev, int num_sets,
                            const uint8_t background[3], void *const *rgb_dev, void *coverage_dev, void *stream);
 
+/* Two more cameras for the calls above; fmgi_camera is the same record. With FMGI_PROJ_PINHOLE each
+   *_proj call is the call without the suffix: same code, bytes, statistics and errors. The other two use the
+   orthonormal frame f = normalized(dir), r = normalized(cross(f, up)), u = cross(r, f), all fp32:
+     ORTHO     the plan at true scale. Sample (i, j) of pixel (x, y) starts at
+               pos + r * pixel * ((x - width/2) + ox_i) - u * pixel * ((y - height/2) + oy_j) and runs along f;
+               pixel is metres per pixel. Walls facing f and walls wholly behind the screen plane are not seen.
+     EQUIRECT  the 360-degree panorama from pos: phi = (x + 0.5 + ox_i) * 2 pi / width, theta = (y + 0.5 + oy_j)
+               * pi / height, ray = normalized(f * (-cos phi sin theta) + r * (-sin phi sin theta) + u * cos theta).
+               Column width / 2 looks along dir, x grows to the right, row 0 is straight up. pixel is not read.
+   ox, oy are fmgi_shade_views' sample offsets; walk, taps and resolve are fmgi_shade_views'. A traced view made
+   by fmgi_view_cache_create_proj gives, through fmgi_view_cache_tiles and _shade, bit for bit what
+   fmgi_output_tiles followed by fmgi_shade_views_proj gives, and info.tests / info.hits are that call's counts.
+   fmgi_view_candidates_proj returns the projection's list: ORTHO keys are the smallest depth along f of a
+   wall's corners (0 if negative), EQUIRECT's list is the pin-hole's without the walls-behind-the-camera cull.
+   Argument errors (FMGI_ERR_ARG, before any device call): those of the call without the suffix in its order
+   (pixel is not checked for EQUIRECT), then a projection that is none of the three, then, for ORTHO and
+   EQUIRECT, a camera whose cross(f, up) has zero or non-finite length. */
+enum { FMGI_PROJ_PINHOLE = 0, FMGI_PROJ_ORTHO = 1, FMGI_PROJ_EQUIRECT = 2 };
+int fmgi_shade_views_proj(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                          int projection, const uint8_t *tiles_rgb, const uint8_t background[3], int samples,
+                          int filter, uint8_t *rgb_out, uint8_t *coverage_out);
+int fmgi_view_candidates_proj(const fmgi_geometry *geo, const fmgi_camera *cam, int projection,
+                              int32_t *wall_idx, float *min_dist, int cap);
+int fmgi_view_cache_create_proj(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
+                                int height, int projection, int samples, int filter, fmgi_view_cache **out);
+/* the projection a traced view was made with (FMGI_PROJ_*), or FMGI_ERR_ARG for a NULL handle */
+int fmgi_view_cache_projection(const fmgi_view_cache *vc);
+
 /* ---- Build-defined device-resident API ---------------------------------------------------------- */
 enum {
     FMGI_OK = 0,

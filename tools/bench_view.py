@@ -13,6 +13,15 @@ its kernel rate per ray relative to k_view_rays' of the line above. (1, nearest)
 fmgi_render_views' rgb and test count at the full size.
 
   python tools/bench_view.py [--reps 3] [--width 4096 --height 3072] [--no-shade]
+
+With --projection ortho | equirect the tool instead times that camera's k_view_shade_proj against the
+pin-hole k_view_shade of the same process at the same ray count (--samples x --samples, --filter): two warm-up
+rounds, then --rounds rounds with the arms alternating, medians with ranges of the kernel time (fmgi_view_stats'
+rays_ms), rays/s, candidates per list, tests per ray and the time per intersects() evaluation. ortho looks down
+on the whole scene, equirect stands at the case's camera position.
+
+  python tools/bench_view.py --projection equirect --width 2048 --height 1024
+  python tools/bench_view.py --projection ortho --width 2048 --height 1536
 """
 import argparse
 import json
@@ -22,6 +31,8 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd")]
+
+import statistics  # noqa: E402
 
 import numpy as np  # noqa: E402
 
@@ -41,13 +52,77 @@ def load_scene(name):
     return scene.box_scene(int(name[3:]), tile_size=2.0)
 
 
+def plan_camera(sc, width, height, margin=1.02):
+    """the orthographic camera above the scene that looks down on all of it: (camera keywords, metres per pixel)"""
+    W = sc.walls
+    pts = np.concatenate([W["pos"], W["pos"] + W["width"], W["pos"] + W["height"],
+                          W["pos"] + W["width"] + W["height"]])[:, :3].astype(np.float64)
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    pixel = margin * max((hi[0] - lo[0]) / width, (hi[1] - lo[1]) / height)
+    pos = (float((lo[0] + hi[0]) / 2), float((lo[1] + hi[1]) / 2), float(hi[2] + 1.0))
+    return dict(pos=pos, dir=(0, 0, -1), up=(0, 1, 0)), float(pixel)
+
+
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def projection_main(a):
+    """k_view_shade_proj<projection> against the pin-hole k_view_shade, arms alternating in one process"""
+    import fmgi
+
+    W, H, S = a.width, a.height, a.samples
+    for name, (sname, _, cam, pixel) in CASES.items():
+        sc = load_scene(sname)
+        n_tiles = sum(int(w["lm"][1]) * int(w["lm"][2]) for w in sc.walls)
+        tiles = np.random.default_rng(5).integers(0, 256, 3 * n_tiles, dtype=np.uint8)
+        pin = fmgi.camera(pixel=pixel * 4096 / W, **cam)
+        if a.projection == "ortho":
+            kw, metres = plan_camera(sc, W, H)
+            new = fmgi.camera(pixel=metres, **kw)
+        else:
+            new = fmgi.camera(pixel=1.0, **cam)
+        arms = {"pinhole": (pin, "pinhole"), a.projection: (new, a.projection)}
+        rows = {k: {"rays_ms": [], "ns_per_test": []} for k in arms}
+        for r in range(2 + a.rounds):
+            order = list(arms) if r % 2 == 0 else list(arms)[::-1]
+            for k in order:
+                c, proj = arms[k]
+                got = fmgi.shade_views(sc, c, W, H, tiles, (7, 8, 9), samples=S, filter=a.filter, projection=proj)
+                st = fmgi.view_stats()
+                if r < 2:
+                    continue
+                rows[k]["rays_ms"].append(st["rays_ms"])
+                rows[k]["ns_per_test"].append(st["rays_ms"] * 1e6 / max(st["tests"], 1))
+                rows[k].update(rays=st["rays"], tests=st["tests"], candidates=st["candidates"], cand_ms=st["cand_ms"],
+                               covered_fraction=float(got["coverage"].mean(dtype=np.float64)) / S ** 2)
+        res = {"metric": "k_view_shade_proj against k_view_shade", "case": name, "walls": int(len(sc.walls)), "width": W,
+               "height": H, "samples": S, "filter": a.filter, "projection": a.projection, "rounds": a.rounds, "n_gpus": 1}
+        for k, row in rows.items():
+            ms = spread(row["rays_ms"])
+            res[k] = {"kernel_ms": ms, "rays_per_s": row["rays"] / (ms["median"] / 1e3), "candidates": row["candidates"],
+                      "tests_per_ray": row["tests"] / row["rays"], "ns_per_test": spread(row["ns_per_test"]),
+                      "cand_ms": row["cand_ms"], "covered_fraction": row["covered_fraction"]}
+        p, q = res["pinhole"]["ns_per_test"], res[a.projection]["ns_per_test"]
+        res["ns_per_test_ratio"] = q["median"] / p["median"]
+        res["within_the_yardsticks_range"] = bool(q["median"] <= p["max"])
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--projection", choices=("ortho", "equirect"), default=None,
+                    help="time this camera's k_view_shade_proj against the pin-hole k_view_shade instead")
+    ap.add_argument("--samples", type=int, default=4, help="--projection: N x N rays per pixel")
+    ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear", help="--projection: the tile filter")
+    ap.add_argument("--rounds", type=int, default=7, help="--projection: timed rounds after two warm-up rounds")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=3072)
     ap.add_argument("--no-shade", action="store_true", help="fmgi_render_views only")
     a = ap.parse_args()
+    if a.projection:
+        return projection_main(a)
     import fmgi
 
     z = np.load(os.path.join(REPO, "tests", "golden", "view_ref.npz"))

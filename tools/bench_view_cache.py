@@ -13,6 +13,11 @@ does not depend on them. The cameras are bench_view.py's, the pixel size scaled 
 the arms, as a caller that drops each picture would.
 
   python tools/bench_view_cache.py [--width 1024 --height 768 --samples 4 --filter bilinear] [--rounds 7] [--free-pictures]
+
+With --projection ortho | equirect the tool instead compares that camera's traced view with the pin-hole's
+of the same process: ViewCache's trace time per ray (k_view_trace_proj against k_view_trace), and tiles + shade per
+scenario for 8 scenarios (device events; the same kernels read the same records). Two warm-up rounds, then --rounds
+rounds with the arms alternating. The cameras are bench_view.py --projection's.
 """
 import argparse
 import json
@@ -35,8 +40,72 @@ def spread(v):
     return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
+def projection_main(a):
+    import torch
+
+    import fmgi
+    from bench_view import CASES, load_scene, plan_camera
+
+    W, H, S, K = a.width, a.height, a.samples, 8
+    dev = "cuda:0"
+    for name in a.cases:
+        sname, _, cam, pixel = CASES[name]
+        sc = load_scene(sname)
+        pin = fmgi.camera(pixel=pixel * 4096 / W, **cam)
+        if a.projection == "ortho":
+            kw, metres = plan_camera(sc, W, H)
+            new = fmgi.camera(pixel=metres, **kw)
+        else:
+            new = fmgi.camera(pixel=1.0, **cam)
+        arms = {"pinhole": pin, a.projection: new}
+        rng = np.random.default_rng(11)
+        texels = [torch.from_numpy((10.0 ** rng.uniform(-3, 1, (sc.num_texels, 4))).astype(np.float32)).to(dev)
+                  for _ in range(K)]
+        ptr = lambda ts: [t.data_ptr() for t in ts]  # noqa: E731
+        rows = {k: {"trace_ms": [], "ns_per_ray": [], "ns_per_test": [], "tiles_shade_ms": []} for k in arms}
+        tiles = rgb = None
+        for r in range(2 + a.rounds):
+            order = list(arms) if r % 2 == 0 else list(arms)[::-1]
+            for k in order:
+                vc = fmgi.ViewCache(sc, arms[k], W, H, S, a.filter, projection=k)
+                info = vc.info()
+                if tiles is None:
+                    tiles = [torch.empty(max(3 * info["tiles"], 1), dtype=torch.uint8, device=dev) for _ in texels]
+                    rgb = [torch.empty((1, H, W, 3), dtype=torch.uint8, device=dev) for _ in texels]
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                torch.cuda.synchronize()
+                ev[0].record()
+                vc.tiles(ptr(texels), SPA, ptr(tiles))
+                vc.shade(ptr(tiles), ptr(rgb), BG)
+                ev[1].record()
+                torch.cuda.synchronize()
+                vc.close()
+                if r < 2:
+                    continue
+                row = rows[k]
+                row["trace_ms"].append(info["trace_ms"])
+                row["ns_per_ray"].append(info["trace_ms"] * 1e6 / info["rays"])
+                row["ns_per_test"].append(info["trace_ms"] * 1e6 / max(info["tests"], 1))
+                row["tiles_shade_ms"].append(ev[0].elapsed_time(ev[1]) / K)
+                row.update(rays=info["rays"], tests=info["tests"], hits=info["hits"], bytes=info["bytes"])
+        res = {"metric": "traced view: k_view_trace_proj against k_view_trace", "case": name, "walls": int(len(sc.walls)),
+               "width": W, "height": H, "samples": S, "filter": a.filter, "projection": a.projection, "scenarios": K,
+               "rounds": a.rounds}
+        for k, row in rows.items():
+            res[k] = {"trace_ms": spread(row["trace_ms"]), "trace_ns_per_ray": spread(row["ns_per_ray"]),
+                      "trace_ns_per_test": spread(row["ns_per_test"]),
+                      "tiles_shade_ms_per_scenario": spread(row["tiles_shade_ms"]), "rays": row["rays"],
+                      "tests_per_ray": row["tests"] / row["rays"], "hit_fraction": row["hits"] / row["rays"],
+                      "bytes": row["bytes"]}
+        p, q = res["pinhole"]["tiles_shade_ms_per_scenario"], res[a.projection]["tiles_shade_ms_per_scenario"]
+        res["tiles_shade_ranges_overlap"] = bool(q["min"] <= p["max"] and p["min"] <= q["max"])
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--projection", choices=("ortho", "equirect"), default=None,
+                    help="compare this camera's traced view with the pin-hole's instead")
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--height", type=int, default=768)
     ap.add_argument("--samples", type=int, default=4)
@@ -47,6 +116,8 @@ def main():
                     help="free arm A's pictures between the arms instead of keeping them until a K's rounds are over: "
                          "at K = 8 the next device work of either arm then waits 11 to 22 ms (DESIGN §16)")
     a = ap.parse_args()
+    if a.projection:
+        return projection_main(a)
     import torch
 
     import fmgi

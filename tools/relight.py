@@ -134,6 +134,8 @@ def parse_args(argv=None):
     ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
     ap.add_argument("--samples", type=int, default=2, help="N x N rays per pixel (1..8)")
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
+    ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
+                    help="--view's camera model: pin-hole, orthographic plan (--pixel metres per pixel), or panorama")
     ap.add_argument("--min-deposits", type=int, default=0,
                     help="adaptive density filter: grow every texel's window until it holds the energy of N "
                          "first-bounce window photons (default 0: no filter)")
@@ -286,7 +288,8 @@ def main(argv=None):
     if a.view:
         # the camera's rays are cast once; every scenario's picture is gathered from its device texels
         vdev = f"cuda:{int(os.environ.get('FMGI_DEVICE', 0))}"  # the device of the geometry-based calls
-        vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter)
+        vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter,
+                            projection=a.projection)
         nbytes = max(3 * vc.info()["tiles"], 1)
         vs = torch.cuda.Stream(device=vdev)
         with torch.cuda.stream(vs):

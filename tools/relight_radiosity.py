@@ -94,6 +94,8 @@ def parse_args(argv=None):
     ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
     ap.add_argument("--samples", type=int, default=2, help="N x N rays per pixel (1..8)")
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
+    ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
+                    help="--view's camera model: pin-hole, orthographic plan (--pixel metres per pixel), or panorama")
     return ap.parse_args(argv)
 
 
@@ -118,7 +120,8 @@ def main(argv=None):
     with torch.cuda.stream(st):
         texels = rc.solve(emit, a.iterations, stream=st)
         if a.view:
-            vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter)
+            vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter,
+                                projection=a.projection)
             nbytes = max(3 * vc.info()["tiles"], 1)
             for k0 in range(0, len(names), fmgi.VIEW_CACHE_MAX_SETS):
                 part = [texels[k] for k in range(k0, min(k0 + fmgi.VIEW_CACHE_MAX_SETS, len(names)))]

@@ -14,6 +14,13 @@ reference's debug raycaster paints.
 With --samples N (N x N rays per pixel, up to 8) and / or --filter bilinear the picture comes from
 fmgi.shade_views instead: supersampled edges and linearly filtered tiles, as a viewer of the tiles draws them.
 
+--projection ortho draws the plan at true scale (parallel rays along --dir, --pixel metres per pixel), --projection
+equirect the 360-degree panorama from --pos (column width / 2 looks along --dir; --pixel is not used, the usual
+picture has --width = 2 * --height); both go through fmgi.shade_views:
+
+  python tools/render_view.py flat.bin --texels out/texels.npy --spa 172413793 --projection ortho --pos 6 5 10 \\
+      --dir 0 0 -1 --up 0 1 0 --pixel 0.01 --width 1400 --height 1100 --samples 4 --filter bilinear -o plan.ppm
+
 A PNG is written next to the PPM when PIL can be imported.
 """
 import argparse
@@ -67,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--background", type=int, nargs=3, default=(0, 0, 0))
     ap.add_argument("--samples", type=int, default=1, help="N x N rays per pixel (1..8)")
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="nearest", help="how a ray reads the tiles")
+    ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
+                    help="camera model: pin-hole, orthographic plan, or equirectangular panorama")
     ap.add_argument("-o", "--output", default="view.ppm")
     a = ap.parse_args(argv)
     import fmgi
@@ -80,11 +89,12 @@ def main(argv=None):
     else:
         tiles = wall_colour_tiles(sc)
     cam = fmgi.camera(a.pos, a.dir, a.up, a.pixel)
-    if a.samples == 1 and a.filter == "nearest":
+    if a.samples == 1 and a.filter == "nearest" and a.projection == "pinhole":
         out = fmgi.render_views(sc, cam, a.width, a.height, tiles_rgb=tiles, background=tuple(a.background))
         hits, unit = int((out["wall"] >= 0).sum()), "pixels"
     else:
-        out = fmgi.shade_views(sc, cam, a.width, a.height, tiles, tuple(a.background), samples=a.samples, filter=a.filter)
+        out = fmgi.shade_views(sc, cam, a.width, a.height, tiles, tuple(a.background), samples=a.samples, filter=a.filter,
+                               projection=a.projection)
         hits, unit = int(out["coverage"].sum(dtype=np.int64)), "rays"
     write_ppm(a.output, out["rgb"][0])
     st = fmgi.view_stats()
