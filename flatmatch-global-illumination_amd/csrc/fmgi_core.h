@@ -183,17 +183,33 @@ FMGI_HD int trunc_div(float x, float y) { return trunc_div_inv(x, y, __builtin_a
 FMGI_HD int trunc_div(float x, float y) { return (int)(x / y); }
 #endif
 
-/* photonmap.cl:108-119: the tile of in-rect coordinates (dx, dy); iwl, ihl ~ 1/wl, 1/hl (one ulp) */
-FMGI_HD int tile_uv(float dx, float dy, float wl, float hl, float iwl, float ihl, int W, int H) {
+/* photonmap.cl:108-119: the tile of in-rect coordinates (dx, dy); iwl, ihl ~ 1/wl, 1/hl (one ulp).
+   0 <= ty < H and W < 2^24, so ty * W is a 24-bit multiply, not the quarter-rate v_mul_lo_u32. NamedMul24 (the
+   wave-locked loop's, tile_uv_m24) names the instruction: __umul24's operand masks are dropped where only the
+   product's low bits are used (a deposit code keeps 22 of the texel's), and the unmasked product was then selected
+   as the full 32-bit multiply after all. The products are equal. */
+template <bool NamedMul24>
+FMGI_HD int tile_uv_t(float dx, float dy, float wl, float hl, float iwl, float ihl, int W, int H) {
     int tx = trunc_div_inv(dx * (float)W, wl, iwl);
     int ty = trunc_div_inv(dy * (float)H, hl, ihl);
     tx = tx < 0 ? 0 : (tx > W - 1 ? W - 1 : tx);
     ty = ty < 0 ? 0 : (ty > H - 1 ? H - 1 : ty);
 #if defined(__HIP_DEVICE_COMPILE__)
-    return (int)__umul24((uint32_t)ty, (uint32_t)W) + tx; /* 0 <= ty < H, W < 2^24: not the quarter-rate v_mul_lo_u32 */
+    if (NamedMul24) {
+        uint32_t p;
+        asm("v_mul_u32_u24 %0, %1, %2" : "=v"(p) : "v"((uint32_t)ty), "v"((uint32_t)W));
+        return (int)p + tx;
+    }
+    return (int)__umul24((uint32_t)ty, (uint32_t)W) + tx;
 #else
     return ty * W + tx;
 #endif
+}
+FMGI_HD int tile_uv(float dx, float dy, float wl, float hl, float iwl, float ihl, int W, int H) {
+    return tile_uv_t<false>(dx, dy, wl, hl, iwl, ihl, W, H);
+}
+FMGI_HD int tile_uv_m24(float dx, float dy, float wl, float hl, float iwl, float ihl, int W, int H) {
+    return tile_uv_t<true>(dx, dy, wl, hl, iwl, ihl, W, H);
 }
 
 /* Warm-up skip-ahead (photonmap.cl:272-275): `r = rand()*40; for (i=0; i<r; i++) rand();` draws

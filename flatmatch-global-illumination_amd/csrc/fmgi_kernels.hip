@@ -2238,6 +2238,16 @@ struct HasAppend<AccLines> {
     static constexpr bool value = true;
 };
 #endif
+/* whether append() is a lane's own business (no ballot, no shared ring position): the wave-locked loop then
+   calls it where the lane deposits */
+template <class Acc>
+struct LaneAppend {
+    static constexpr bool value = false;
+};
+template <>
+struct LaneAppend<AccShared> {
+    static constexpr bool value = true;
+};
 /* the LDS region of an appending accumulation: the wave's ring (AccStreamT), the workgroup's tile lines
    (AccLines) */
 template <class Acc>
@@ -2714,6 +2724,23 @@ __device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
  * The lightmap and every counter are integer sums over items: which lane traces an item, and when, changes
  * no bit. Every loop is bounded by the item counter, the photons of an item and the depth.
  * Scans and escapes are counted per wave from the lane masks (s_bcnt1), not per lane.
+ *
+ * The AccShared instances (kTrim: box200's product instance) run a trimmed form of the depth loop, measured for
+ * them alone (profiles/loop_trim); the other accumulations keep the loop as it was, and their registers:
+ *  - the emission and the bounce's sample are two arms of the scalar branch on depth (no fold, no emitter field
+ *    in the bounce's sampler);
+ *  - the hit point is complete before the mirror and the mirror is an arm of its own after the diffuse one, so
+ *    it writes dir in place (as the else of a three-way join it wrote temporaries, to which the diffuse lanes'
+ *    dir was copied, and back);
+ *  - the last bounce's RNG jump stays behind the scalar branch on depth (as a select its quarter-rate multiply
+ *    ran at every depth), and the tile product is the 24-bit multiply by name (tile_uv_m24);
+ *  - nothing is counted on the straight path: a ballot of `alive` or of an escape flag made the lane mask a
+ *    0 / 1 register and compared that again, at every scan. A lane counts its escapes, and the scans those cut
+ *    its photons short of FMGI_MAX_DEPTH each, where a photon escapes; the wave's scans are FMGI_MAX_DEPTH a
+ *    photon less these (32 bits: a lane traces a few dozen items per launch);
+ *  - AccShared::append is a lane's own business (LaneAppend) and is called where the lane deposits, so neither
+ *    the code nor `dep` is a value joined over the escape and the parked lanes.
+ * The two empty asm statements only steer the compiler; whether they still do is read off the listing.
  */
 template <class Scan, class Acc, bool TRACE>
 __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a) {
@@ -2735,8 +2762,11 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
     bool win = false;
     uint64_t item = 0; /* (TRACE) */
     int nev = 0;       /* (TRACE) */
+    constexpr bool kTrim = LaneAppend<Acc>::value; /* the trimmed loop (above) */
     unsigned long long w_ph = 0, w_scan = 0; /* the wave's counts of one launch (wave-uniform) */
     uint32_t w_esc = 0;
+    uint32_t n_esc = 0, n_cut = 0; /* (kTrim) per lane: escapes, and the scans they cut short */
+    (void)n_esc; (void)n_cut;
     ScanStats sst;
     WaveStream ws;
     sst.clk.reset();
@@ -2782,28 +2812,46 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
             for (int depth = 0; depth < FMGI_MAX_DEPTH; depth++) {
                 bool dep = false, esc = false;
                 uint32_t code = 0;
-                w_scan += (uint32_t)__popcll(__ballot(alive));
+                if constexpr (!kTrim) w_scan += (uint32_t)__popcll(__ballot(alive));
                 if (alive) {
                     /* ---- stage 1: the photon's emission, then the iteration's one direction sample ---- */
-                    float edx = 0, edy = 0;
-                    if (depth == 0) {
+                    if constexpr (!kTrim) {
+                        float edx = 0, edy = 0;
+                        if (depth == 0) {
+                            const SrcDev S = load_src<true>(a, s_img, srci);
+                            col = win ? mkf3(18, 18, 18) : mkf3(16, 16, 18); /* photonmap.cl:167-169 */
+                            sid = win ? (512 + 1) : 1;
+                            edx = rng_next(rng);
+                            edy = rng_next(rng);
+                            sn = mkf3(S.nx, S.ny, S.nz);
+                            sbu = mkf3(S.bux, S.buy, S.buz);
+                            sbv = mkf3(S.bvx, S.bvy, S.bvz);
+                        }
+                        sst.clk.lap(ST_START);
+                        if (depth == 0 || pend) dir = sample_dir(rng, sn, sbu, sbv, depth == 0 && win);
+                        if (depth == 0) {
+                            const SrcDev S = load_src<true>(a, s_img, srci);
+                            pos = add3(add3(add3(mkf3(S.px, S.py, S.pz), mul3(mkf3(S.wx, S.wy, S.wz), edx)),
+                                            mul3(mkf3(S.hx, S.hy, S.hz), edy)),
+                                       mul3(dir, 1e-5f));
+                        } else {
+                            pos = add3(pos, mul3(dir, 1e-5f)); /* photonmap.cl:261 */
+                        }
+                    } else if (depth == 0) { /* (kTrim: one arm per depth, see above) */
                         const SrcDev S = load_src<true>(a, s_img, srci);
                         col = win ? mkf3(18, 18, 18) : mkf3(16, 16, 18); /* photonmap.cl:167-169 */
                         sid = win ? (512 + 1) : 1;
-                        edx = rng_next(rng);
-                        edy = rng_next(rng);
-                        sn = mkf3(S.nx, S.ny, S.nz);
-                        sbu = mkf3(S.bux, S.buy, S.buz);
-                        sbv = mkf3(S.bvx, S.bvy, S.bvz);
-                    }
-                    sst.clk.lap(ST_START);
-                    if (depth == 0 || pend) dir = sample_dir(rng, sn, sbu, sbv, depth == 0 && win);
-                    if (depth == 0) {
-                        const SrcDev S = load_src<true>(a, s_img, srci);
+                        const float edx = rng_next(rng);
+                        const float edy = rng_next(rng);
+                        sst.clk.lap(ST_START);
+                        dir = sample_dir(rng, mkf3(S.nx, S.ny, S.nz), mkf3(S.bux, S.buy, S.buz),
+                                         mkf3(S.bvx, S.bvy, S.bvz), win);
                         pos = add3(add3(add3(mkf3(S.px, S.py, S.pz), mul3(mkf3(S.wx, S.wy, S.wz), edx)),
                                         mul3(mkf3(S.hx, S.hy, S.hz), edy)),
                                    mul3(dir, 1e-5f));
                     } else {
+                        sst.clk.lap(ST_START);
+                        if (pend) dir = sample_dir(rng, sn, sbu, sbv, false);
                         pos = add3(pos, mul3(dir, 1e-5f)); /* photonmap.cl:261 */
                     }
                     pend = false;
@@ -2818,31 +2866,64 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
                     sbv = mkf3(h.bvx, h.bvy, h.bvz);
                     if (h.best == INFINITY) { /* photonmap.cl:208-209: parked until the wave's next photon */
                         alive = false;
-                        esc = true;
+                        if constexpr (kTrim) {
+                            n_esc++;
+                            n_cut += (uint32_t)(FMGI_MAX_DEPTH - 1 - depth);
+                        } else {
+                            esc = true;
+                        }
                         if (uni(a.src_cost))
                             atomicAdd(a.src_cost + srci, 0ull - (unsigned long long)(FMGI_MAX_DEPTH - 1 - depth));
                     } else {
                         /* ---- stage 3: hit (photonmap.cl:216-258) ---- */
                         pos = add3(pos, mul3(dir, h.best));
+                        /* (kTrim: the hit point is in its registers before the mirror, which then needs no old dir) */
+                        if constexpr (kTrim) asm volatile("" : "+v"(pos.x), "+v"(pos.y), "+v"(pos.z));
                         const f3 hn = mkf3(h.nx, h.ny, h.nz);
-                        const int texel = h.base + tile_uv(h.dx, h.dy, h.wl, h.hl, h.iwl, h.ihl, h.W, h.H);
-                        const bool last = depth + 1 == FMGI_MAX_DEPTH;
-                        if (pos.z > 4.99999965541064739227294921875e-4f || rng_next(rng) > 0.75f) {
-                            const bool floor = pos.z < 1e-5f;
-                            if (floor) {
-                                col.y *= 0.85f;
-                                col.z *= 0.7f;
-                            }
-                            col = mul3(col, 0.9f);
-                            sid = (sid & 512) | ((sid & 511) << 1) | (floor ? 1 : 0);
-                            if (last) {
-                                rng = lcg2(rng); /* the direction of a photon that ends here is never used */
+                        const int texel = h.base + (kTrim ? tile_uv_m24(h.dx, h.dy, h.wl, h.hl, h.iwl, h.ihl, h.W, h.H)
+                                                          : tile_uv(h.dx, h.dy, h.wl, h.hl, h.iwl, h.ihl, h.W, h.H));
+                        const bool last = depth + 1 == FMGI_MAX_DEPTH; /* (wave-uniform) */
+                        /* (double)pos.z > 0.0005 (photonmap.cl:236), else the roulette's draw */
+                        if constexpr (!kTrim) {
+                            if (pos.z > 4.99999965541064739227294921875e-4f || rng_next(rng) > 0.75f) {
+                                const bool floor = pos.z < 1e-5f;
+                                if (floor) {
+                                    col.y *= 0.85f;
+                                    col.z *= 0.7f;
+                                }
+                                col = mul3(col, 0.9f);
+                                sid = (sid & 512) | ((sid & 511) << 1) | (floor ? 1 : 0);
+                                if (last) {
+                                    rng = lcg2(rng); /* the direction of a photon that ends here is never used */
+                                } else {
+                                    pend = true; /* sampled at the top of the next iteration */
+                                }
                             } else {
-                                pend = true; /* sampled at the top of the next iteration */
+                                const float two = 2.0f * dot3(hn, dir);
+                                dir = sub3(dir, mul3(hn, two));
                             }
                         } else {
-                            const float two = 2.0f * dot3(hn, dir);
-                            dir = sub3(dir, mul3(hn, two));
+                            bool diffuse = pos.z > 4.99999965541064739227294921875e-4f;
+                            if (!diffuse) diffuse = rng_next(rng) > 0.75f;
+                            if (diffuse) {
+                                const bool floor = pos.z < 1e-5f;
+                                if (floor) {
+                                    col.y *= 0.85f;
+                                    col.z *= 0.7f;
+                                }
+                                col = mul3(col, 0.9f);
+                                sid = (sid & 512) | ((sid & 511) << 1) | (floor ? 1 : 0);
+                                if (last) {
+                                    rng = lcg2(rng);
+                                    asm volatile(""); /* (keeps this arm a scalar branch, not a select) */
+                                } else {
+                                    pend = true;
+                                }
+                            }
+                            if (!diffuse) { /* (an arm of its own after the diffuse one: dir in place) */
+                                const float two = 2.0f * dot3(hn, dir);
+                                dir = sub3(dir, mul3(hn, two));
+                            }
                         }
                         Acc::deposit(a, texel, sid, col);
                         dep = true;
@@ -2860,11 +2941,12 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
                             ((EventDev *)a.events)[(item - a.item_begin) * FMGI_EVENTS_PER_ITEM + nev] = e;
                             nev++;
                         }
+                        if constexpr (kTrim) Acc::append(a, ws, ring, true, code);
                     }
                     sst.clk.lap(ST_HIT);
                 }
-                w_esc += (uint32_t)__popcll(__ballot(esc));
-                if constexpr (HasAppend<Acc>::value) Acc::append(a, ws, ring, dep, code);
+                if constexpr (!kTrim) w_esc += (uint32_t)__popcll(__ballot(esc));
+                if constexpr (HasAppend<Acc>::value && !kTrim) Acc::append(a, ws, ring, dep, code);
                 sst.clk.lap(ST_APPEND);
             }
         }
@@ -2879,6 +2961,10 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
     }
     if constexpr (HasAppend<Acc>::value) Acc::finish(a, ws, ring);
 
+    if constexpr (kTrim) {
+        w_esc = (uint32_t)wave_sum(n_esc);
+        w_scan = w_ph * FMGI_MAX_DEPTH - wave_sum(n_cut); /* (an escape is a scan) */
+    }
     if ((threadIdx.x & 63) == 0) {
         if (w_ph) atomicAdd(a.stats + KSTAT_PHOTONS, w_ph);
         if (w_scan) atomicAdd(a.stats + KSTAT_SCANS, w_scan);
