@@ -22,6 +22,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path[:0] = [os.path.join(REPO, "flatmatch-global-illumination_amd"), os.path.join(REPO, "tests")]
+import emitter_scenes  # noqa: E402
 import offaxis_scenes  # noqa: E402
 from fmgi import scene  # noqa: E402
 
@@ -44,6 +45,8 @@ def main():
         "crossing": (offaxis_scenes.get("crossing"), 3),
         "open_tilted": (offaxis_scenes.get("open_tilted"), 5),
         "tilted12": (offaxis_scenes.get("tilted12"), 9),
+        # tests/emitter_scenes.py: a window and a lamp that are not axis-aligned, as hit geometry and as emitters
+        "tilted_emitters": (emitter_scenes.get("tilted_emitters"), 11),
     }
     if "--example" in sys.argv:
         scenes = {"example": (scene.load_geometry(os.path.join(HERE, "example_geometry.bin"), "example"), 1)}

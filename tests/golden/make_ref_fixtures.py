@@ -27,6 +27,7 @@ sys.path[:0] = [os.path.join(REPO, "oracle"), os.path.join(REPO, "flatmatch-glob
                 os.path.join(REPO, "tests")]
 
 import bake_scenes  # noqa: E402
+import emitter_scenes  # noqa: E402
 import fm_oracle as O  # noqa: E402
 from fmgi import scene as S  # noqa: E402
 
@@ -74,6 +75,13 @@ def main():
     # rects, whose hits the kernel's index-order scan gives to the first of them
     cases += [(name, bake_scenes.get(name), bake_scenes.SPA, [(0, range(0, 32))], ("strict",))
               for name in ("open_box", "tilted12", "stacked14")]
+    # tests/emitter_scenes.py (strict only): gids 0..31 of the first launch of every source: windows and lights through
+    # either branch of the sampler basis, emitters without a zero component, and first rays from outside the walls
+    for name in ("lamps", "tilted_emitters", "threshold", "outside"):
+        sc = emitter_scenes.get(name)
+        L = O.schedule_with_offsets(sc, bake_scenes.SPA, offs)
+        firsts = [int(np.flatnonzero(L["source"] == s)[0]) for s in range(len(sc.sources))]
+        cases.append((name, sc, bake_scenes.SPA, [(li, range(0, 32)) for li in firsts], ("strict",)))
     only = os.environ.get("FMGI_REF_CASES")  # e.g. "box2000,apartment30": regenerate a subset
     if only:
         cases = [c for c in cases if c[0] in only.split(",")]

@@ -20,6 +20,7 @@ import sys
 import numpy as np
 import pytest
 
+import emitter_scenes
 import fmgi
 import rad_cache_cases as CASES
 import rad_solve_restate as R
@@ -82,6 +83,24 @@ def test_create_and_reference_palette(torch_cuda, libc, name):
     assert libc.rand() == first, "solve draws nothing"
     assert got.shape == (1, sc.num_texels, 4) and got.is_cuda
     _same(got[0], tex)
+
+
+def test_reference_palette_on_tilted_emitters(torch_cuda, libc):
+    """tests/emitter_scenes.py's tilted window and lamp, emitters and hit geometry of the cache: its reference
+    palette equals fmgi.radiosity from the same libc position (which tests/test_offaxis_radiosity.py compares with
+    the oracle and the reference)"""
+    sc = emitter_scenes.get("tilted_emitters")
+    CASES.seed(libc, "tilted_emitters")
+    tex = fmgi.radiosity(sc)
+    nxt = libc.rand()
+    CASES.seed(libc, "tilted_emitters")
+    rc = fmgi.RadCache(sc)
+    try:
+        assert libc.rand() == nxt
+        assert (rc.info["windows"], rc.info["lights"]) == (1, 1)
+        _same(rc.solve(fmgi.rad_reference_emit(sc)[None], 7)[0], tex)
+    finally:
+        rc.close()
 
 
 @pytest.mark.parametrize("rounds", ALL_ROUNDS)

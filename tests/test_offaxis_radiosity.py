@@ -8,6 +8,9 @@ and the `id < 0` path of k_rad_gather have not run, and the candidate sort has o
                      (4,2) texels, so the mip chain takes its 1-D steps
   crossing           partitions inside the box
   tilted56/tilted57  256 and 257 rects: sort_n 256 (no padding) and 512 (255 pad keys)
+  tilted_emitters    tests/emitter_scenes.py: a window and a lamp that are not axis-aligned, which the backend puts
+                     into its rect list as hit geometry and as emitters (the window with its 32 x 16 grid: the
+                     backend gives every emitter a texel base of its own behind the walls', radiosityNative.c:111-126)
 
   reference (oracle/_ref/rad_ref, tests/golden/rad_ref.json) == oracle/rad_oracle.c          (CPU)
   GPU texels and sourceTexelIds == oracle bit for bit; the libc stream left in place;
@@ -21,13 +24,18 @@ import numpy as np
 import pytest
 
 import fm_oracle as O
+import emitter_scenes
 import fmgi
 import offaxis_scenes as S
 from conftest import GOLDEN
 
-PINNED = {"crossing": 3, "open_tilted": 5, "tilted12": 9}  # name: seed of the reference run
-GPU_SCENES = ["crossing", "open_tilted", "tilted56", "tilted57"]
+PINNED = {"crossing": 3, "open_tilted": 5, "tilted12": 9, "tilted_emitters": 11}  # name: seed of the reference run
+GPU_SCENES = ["crossing", "open_tilted", "tilted56", "tilted57", "tilted_emitters"]
 SEED, PRE = 5, 777  # the GPU cases start mid-stream, except where the reference fixture fixes the seed
+
+
+def _scene(name):
+    return emitter_scenes.get(name) if name in emitter_scenes.NAMES else S.get(name)
 
 
 def _sha(a):
@@ -55,7 +63,7 @@ def _oracle(libc, name):
     """the oracle's (texels, sids, next rand()) from the case's stream position; computed once, read-only"""
     if name not in _cache:
         _seed(libc, name)
-        tex, sids = O.radiosity(S.get(name), with_sids=True)
+        tex, sids = O.radiosity(_scene(name), with_sids=True)
         nxt = libc.rand()
         tex.setflags(write=False)
         sids.setflags(write=False)
@@ -72,7 +80,7 @@ def test_lightmap_shapes_of_the_open_scene():
 def test_oracle_reproduces_reference(name, libc):
     ref = _fixtures()[name]
     assert ref["seed"] == PINNED[name]
-    sc = S.get(name)
+    sc = _scene(name)
     tex, sids, nxt = _oracle(libc, name)
     assert nxt == ref["next_rand"]
     first = [float(tex[int(w["lm"][0]), 0]) for w in sc.walls]
@@ -103,7 +111,7 @@ def test_rect_counts_at_the_power_of_two_edge(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", GPU_SCENES)
 def test_gpu_equals_oracle(torch_cuda, libc, name):
-    sc = S.get(name)
+    sc = _scene(name)
     t_o, s_o, nxt = _oracle(libc, name)
     _seed(libc, name)
     t_g, s_g = fmgi.radiosity(sc, with_sids=True)

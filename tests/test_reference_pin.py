@@ -5,12 +5,16 @@ reference photonmap.cl, compiled for gfx950 with ROCm's OpenCL device libraries 
 launched one work item per launch on a zeroed lightColors buffer. Here the oracle's fp32 per-item sum
 (fm_oracle.trace_item_f32: the same deposits added in the same order) must reproduce those lightmaps:
   strict  (IEEE div/sqrt, no contraction = the oracle contract, with the OpenCL builtins as ROCm builds
-          them for gfx950): every item bit for bit -- 528 items over eight scenes: example.png (configs 1
+          them for gfx950): every item bit for bit -- 912 items over twelve scenes: example.png (configs 1
           and 2, incl. the config-2 schedule's last launches), box200 (config 3 and the last launches of config 4),
           box2000 (config 5), the generated 30-room layout, and 32 items each of three scenes of
           tests/bake_scenes.py (strict only): open_box (most photons escape, photonmap.cl:208), tilted12 (rects
           that are not axis-aligned) and stacked14 (15 coincident rects: the index-order scan's strict
-          `d < closest`, photonmap.cl:189-206, gives every hit to the first);
+          `d < closest`, photonmap.cl:189-206, gives every hit to the first), and 32 items of every source of four
+          scenes of tests/emitter_scenes.py (strict only): lamps (96: lights through either branch of the sampler
+          basis, photonmap.cl:65-70), tilted_emitters (64: width, height and n without a zero component in
+          photonmap.cl:27-74 and :181), threshold (128: |n.z| on either side of 0.999999f) and outside (96: first
+          rays from outside the walls, a lamp that straddles the ceiling);
   relaxed (-cl-unsafe-math-optimizations): the same deposit totals, most items bit for bit -- relaxed
           math moves a few hit points across texel boundaries, it does not change colours.
 """
@@ -40,6 +44,10 @@ def _scene(name, example_scene, box200, box2000):
         import bake_scenes
 
         return bake_scenes.get(name)
+    if name in ("lamps", "tilted_emitters", "threshold", "outside"):
+        import emitter_scenes
+
+        return emitter_scenes.get(name)
     if name == "apartment30":
         return scene.load_geometry(os.path.join(GOLDEN, "apartment30_geometry.bin"), "apartment30")
     return {"example": example_scene, "example_late": example_scene, "box200": box200, "box200_late": box200,
@@ -49,13 +57,15 @@ def _scene(name, example_scene, box200, box2000):
 # (fixture, items): launches 0/7 of config 1 and item 1000.. of config 3 (round 1); late launches of the
 # config-2 and config-4 schedules (rng offsets deep in the glibc prefix), the first and last launch of
 # config 5 (box2000) and the generated 30-room layout (round 2); launch 0, gids 0..31 of an open box, a box with
-# tilted rects and a box with 15 coincident floors (tests/bake_scenes.py)
+# tilted rects and a box with 15 coincident floors (tests/bake_scenes.py); gids 0..31 of the first launch of every
+# source of four scenes of tests/emitter_scenes.py
 PINNED = [("example", 128), ("box200", 48), ("example_late", 64), ("box200_late", 64), ("box2000", 64),
-          ("apartment30", 64), ("open_box", 32), ("tilted12", 32), ("stacked14", 32)]
+          ("apartment30", 64), ("open_box", 32), ("tilted12", 32), ("stacked14", 32),
+          ("lamps", 96), ("tilted_emitters", 64), ("threshold", 128), ("outside", 96)]
 
 
 def test_pinned_item_count():
-    assert sum(n for _, n in PINNED) == 528  # the figure README.md and DESIGN.md §2 quote
+    assert sum(n for _, n in PINNED) == 912  # the figure README.md and DESIGN.md §2 quote
 
 
 @pytest.mark.parametrize("name,n_items", PINNED)
