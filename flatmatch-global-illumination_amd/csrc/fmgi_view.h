@@ -128,6 +128,52 @@ struct TraceProjArgs {
     float kphi, ktheta;
 };
 
+/*
+ * The glossy floor (fmgi_*_gloss): a sample that lands at the bake's mirror height casts one mirror
+ * ray and blends what it sees into its colour. The mirror ray walks a second list per camera, every wall of the
+ * scene keyed by its distance to the camera position (k_view_candidates_proj<FMGI_VIEW_MIRROR>: no culls), with
+ * the walk's lower bound moved to the camera: the path camera -> floor -> hit is base + best long, and no wall is
+ * nearer to the camera than its key. The kernels are k_view_shade_gloss<P>, k_view_trace_gloss<P> and
+ * k_view_resolve_gloss<BILINEAR>; the kernels above are not touched.
+ *
+ * A traced view keeps, next to its primary records, one mirror record per sample at the same [c][n][y][x] index and
+ * in the same NEAREST / BILINEAR form; its first word is FMGI_VIEW_NO_MIRROR for a sample that does not mirror and
+ * FMGI_VIEW_MISS for a mirror ray that hit nothing.
+ */
+#define FMGI_VIEW_MIRROR 3 /* k_view_candidates_proj only: the mirror list */
+#define FMGI_VIEW_NO_MIRROR 0xFFFFFFFEu
+#define FMGI_VIEW_MIRROR_Z 4.99999965541064739227294921875e-4f /* (double)z > 0.0005 in fp32, as k_bake has it */
+
+struct GlossArgs {
+    const unsigned long long *mkeys; /* [ncams][sort_n]: the mirror lists, nrects entries each */
+    unsigned long long *counters;    /* three counters: mirror rays, mirror hits, mirror tests */
+    float gloss;                     /* the mirror's weight; the trace does not read it */
+};
+
+struct ShadeGlossArgs {
+    ShadeProjArgs q;
+    GlossArgs g;
+};
+
+struct TraceGlossArgs {
+    TraceProjArgs q;
+    GlossArgs g;
+    void *mrecords; /* the mirror records of this launch's cameras */
+};
+
+struct ResolveGlossArgs {
+    ResolveArgs r;
+    const void *mrecords;
+    float gloss;
+};
+
+/* a.keys and a.counts: the mirror lists' own buffers */
+hipError_t fmgi_view_launch_candidates_mirror(const ViewArgs &a, hipStream_t s);
+/* projection: FMGI_VIEW_PINHOLE, _ORTHO or _EQUIRECT */
+hipError_t fmgi_view_launch_shade_gloss(const ShadeGlossArgs &a, int projection, hipStream_t s);
+hipError_t fmgi_view_launch_trace_gloss(const TraceGlossArgs &t, int projection, hipStream_t s);
+hipError_t fmgi_view_launch_resolve_gloss(const ResolveGlossArgs &r, hipStream_t s);
+
 hipError_t fmgi_view_launch_candidates_proj(const ViewArgs &a, int projection, hipStream_t s);
 hipError_t fmgi_view_launch_shade_proj(const ShadeProjArgs &a, int projection, hipStream_t s);
 hipError_t fmgi_view_launch_trace_proj(const TraceProjArgs &t, int projection, hipStream_t s);

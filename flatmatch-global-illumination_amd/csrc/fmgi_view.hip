@@ -5,6 +5,7 @@
  * Arithmetic: IEEE fp32 in the reference's source order (gcc -O2 -msse3, no FMA), contraction off, with
  * the helpers the radiosity backend uses (fmgi_rect_dev.h). The orthographic and equirectangular cameras
  * (no reference program) are the _proj instances; they call the pin-hole kernels' device functions.
+ * The glossy floor's mirror bounce (no reference program) is the _gloss kernels on the same functions.
  */
 #include <hip/hip_runtime.h>
 
@@ -259,7 +260,8 @@ __global__ __launch_bounds__(256) void k_view_shade(ShadeArgs s) {
  *   ORTHO     walls that face against f and have a corner at depth >= 0 along f; the key is the smallest
  *             corner depth, clamped to 0 from below (every ray of the camera has direction f, so a hit's
  *             distance is a depth between its wall's corner depths);
- *   EQUIRECT  the pin-hole's list without isBehindRay: the rays leave the camera in every direction.
+ *   EQUIRECT  the pin-hole's list without isBehindRay: the rays leave the camera in every direction;
+ *   MIRROR    every wall, keyed as the pin-hole keys it: the list the mirror rays of any projection walk.
  */
 template <int P>
 __global__ __launch_bounds__(256) void k_view_candidates_proj(ViewArgs a) {
@@ -287,6 +289,9 @@ __global__ __launch_bounds__(256) void k_view_candidates_proj(ViewArgs a) {
                 const float m12 = e1 < e2 ? e1 : e2, m34 = e3 < e4 ? e3 : e4, m = m12 < m34 ? m12 : m34;
                 keep = dot(rn, f) < 0 && !(e1 < 0 && e2 < 0 && e3 < 0 && e4 < 0);
                 md = m < 0 ? 0.0f : m;
+            } else if constexpr (P == FMGI_VIEW_MIRROR) {
+                keep = true;
+                md = min_dist(pos, w, h, rn, cam);
             } else {
                 keep = !(dot(rn, sub(pos, cam)) > 0);
                 md = keep ? min_dist(pos, w, h, rn, cam) : 0.0f;
@@ -620,6 +625,365 @@ __global__ __launch_bounds__(256) void k_view_resolve(ResolveArgs r) {
     if (r.cov_out) r.cov_out[o] = (uint8_t)cov;
 }
 
+/*
+ * The glossy floor. view_walk over the mirror list, the lower bound moved to the camera position:
+ * base = |Q - camPos|, so base + best is the length of the path camera -> floor -> hit, and no wall is nearer to
+ * the camera than its key. The lanes of a wave that mirror enter together at entry 0, so the entry's index is
+ * uniform over the lanes still walking and keys and rectangles are read once per wave; Q, d2, base and best are
+ * the lane's own. The loop ends after the N walls of the list at the latest.
+ */
+__device__ __forceinline__ int view_walk_mirror(const ViewArgs &a, const unsigned long long *mkeys, int N, v3 Q, v3 d2,
+                                                float base, float &best, unsigned long long &tests) {
+    best = INFINITY;
+    int wall2 = -1;
+    for (int i = 0; i < N; i++) {
+        const unsigned long long key = mkeys[i];
+        const float md = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32)));
+        if ((base + best) < md) break;
+        const int idx = __builtin_amdgcn_readfirstlane((int)(uint32_t)key);
+        tests++;
+        const float dn = rect_intersects(a.hits[idx], Q, d2, best);
+        if (dn < 0) continue;
+        if (dn <= best) {
+            wall2 = idx;
+            best = dn;
+        }
+    }
+    return wall2;
+}
+
+/* does the sample that hit at P mirror: the bake's test (k_bake, photonmap.cl:236), whatever the wall */
+__device__ __forceinline__ bool mirrors(v3 P) { return !(P.z > FMGI_VIEW_MIRROR_Z); }
+
+/* the mirror ray of a hit at P on wall t (photonmap.cl:253, :261; d2 keeps its length) and its walk */
+__device__ __forceinline__ int mirror_walk(const ViewArgs &a, const unsigned long long *mkeys, v3 cam, const AoRect &t, v3 P,
+                                           v3 dir, v3 &Q, v3 &d2, float &best, unsigned long long &tests) {
+    const v3 n = mk(t.nx, t.ny, t.nz);
+    const float two = 2.0f * dot(n, dir);
+    d2 = sub(dir, mul(n, two));
+    Q = add(P, mul(d2, 1e-5f));
+    return view_walk_mirror(a, mkeys, a.nrects, Q, d2, len3(sub(Q, cam)), best, tests);
+}
+
+/* sample (j, i)'s ray of pixel (px, py): the pin-hole's, k_view_shade_proj's ORTHO and EQUIRECT */
+template <int P>
+__device__ __forceinline__ void sample_ray(const ViewCam &V, v3 cam, float fx, float fy, float2 phi, float st, float ct,
+                                           v3 &src, v3 &dir) {
+    src = cam;
+    if constexpr (P == FMGI_VIEW_PINHOLE) {
+        dir = view_dir(V, cam, fx, fy);
+    } else if constexpr (P == FMGI_VIEW_ORTHO) {
+        src = ortho_origin(V, cam, fx, fy);
+        dir = mk(V.dx, V.dy, V.dz);
+    } else {
+        dir = equirect_dir(V, phi.x, phi.y, st, ct);
+    }
+}
+
+/* a hit's colour as k_view_shade taps it, before fix8 */
+__device__ __forceinline__ void tap_colour(const uint32_t *T, const RadRect &tr, float u, float v, bool bilinear, float &c0,
+                                           float &c1, float &c2) {
+    if (!bilinear) {
+        const uint32_t w = T[clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1)];
+        c0 = (float)(w & 255), c1 = (float)((w >> 8) & 255), c2 = (float)((w >> 16) & 255);
+        return;
+    }
+    int xa, xb, ya, yb;
+    float fu, fv;
+    tap_axis(u, tr.s1, xa, xb, fu);
+    tap_axis(v, tr.s2, ya, yb, fv);
+    const uint32_t w00 = T[ya * tr.s1 + xa], w01 = T[ya * tr.s1 + xb], w10 = T[yb * tr.s1 + xa], w11 = T[yb * tr.s1 + xb];
+#define FMGI_CH(sh)                                                                                        \
+    lerp2(fv, lerp2(fu, (float)((w00 >> sh) & 255), (float)((w01 >> sh) & 255)),                         \
+          lerp2(fu, (float)((w10 >> sh) & 255), (float)((w11 >> sh) & 255)))
+    c0 = FMGI_CH(0), c1 = FMGI_CH(8), c2 = FMGI_CH(16);
+#undef FMGI_CH
+}
+
+/* a hit's record as k_view_trace writes it */
+__device__ __forceinline__ uint4 tap_record(uint32_t first, const RadRect &tr, float u, float v, bool bilinear) {
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    if (!bilinear) {
+        rec.x = first + (uint32_t)(clampi(cvt_x86(v), 0, tr.s2 - 1) * tr.s1 + clampi(cvt_x86(u), 0, tr.s1 - 1));
+    } else {
+        int xa, xb, ya, yb;
+        float fu, fv;
+        tap_axis(u, tr.s1, xa, xb, fu);
+        tap_axis(v, tr.s2, ya, yb, fv);
+        rec.x = (first + (uint32_t)(ya * tr.s1 + xa)) | ((uint32_t)(xb != xa) << 31);
+        rec.y = first + (uint32_t)(yb * tr.s1 + xa);
+        rec.z = __float_as_uint(fu);
+        rec.w = __float_as_uint(fv);
+    }
+    return rec;
+}
+
+/*
+ * k_view_shade / k_view_shade_proj with the mirror bounce: the same pixel mapping, sample loop, primary walk and
+ * taps. A sample that hit and mirrors walks the mirror list inside one branch after the primary walk, taps the
+ * wall its mirror ray hit (or takes the background) and blends the two colours before fix8. The second walk runs
+ * whether or not a picture is asked for, so that the counts do not depend on the outputs.
+ */
+template <int P>
+__global__ __launch_bounds__(256) void k_view_shade_gloss(ShadeGlossArgs ga) {
+    const ShadeProjArgs &q = ga.q;
+    const ShadeArgs &s = q.s;
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    __shared__ PhiTable phis; /* EQUIRECT only */
+    unsigned long long tests = 0, mtests = 0;
+    unsigned int mrays = 0, mhits = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n, *mkeys = ga.g.mkeys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool colour = a.rgb_out != nullptr, bilinear = s.filter != 0;
+        const float gloss = ga.g.gloss;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        const float b0 = (float)(a.background & 255), b1 = (float)((a.background >> 8) & 255),
+                    b2 = (float)((a.background >> 16) & 255);
+        const int bg0 = fix8(b0), bg1 = fix8(b1), bg2 = fix8(b2);
+        if constexpr (P == FMGI_VIEW_EQUIRECT) phi_table(phis, tid, x, S, s.offs, q.kphi);
+        int sum0 = 0, sum1 = 0, sum2 = 0, cov = 0;
+        for (int j = 0; j < S; j++) {
+            float fy = 0.0f, st = 0.0f, ct = 0.0f;
+            if constexpr (P == FMGI_VIEW_EQUIRECT) fmgi_sincosf(((float)y + (0.5f + s.offs[j])) * q.ktheta, &st, &ct);
+            else fy = -V.pixel * (py + s.offs[j]);
+            for (int i = 0; i < S; i++) {
+                float fx = 0.0f;
+                float2 phi = make_float2(0.0f, 0.0f);
+                if constexpr (P == FMGI_VIEW_EQUIRECT) phi = phis.sc[i][tid];
+                else fx = V.pixel * (px + s.offs[i]);
+                v3 src, dir;
+                sample_ray<P>(V, cam, fx, fy, phi, st, ct, src, dir);
+                float dist;
+                const int target = view_walk(a, keys, C, src, dir, dist, tests);
+                if (target < 0) {
+                    sum0 += bg0, sum1 += bg1, sum2 += bg2;
+                    continue;
+                }
+                cov++;
+                float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+                if (colour) {
+                    const RadRect tr = a.rects[target];
+                    float u, v;
+                    view_uv(a.hits[target], tr, src, dir, dist, u, v);
+                    tap_colour(s.tiles + a.first_tile[target], tr, u, v, bilinear, v0, v1, v2);
+                }
+                const v3 Pt = add(src, mul(dir, dist));
+                if (mirrors(Pt)) {
+                    v3 Q, d2;
+                    float best;
+                    const int wall2 = mirror_walk(a, mkeys, cam, a.hits[target], Pt, dir, Q, d2, best, mtests);
+                    mrays++;
+                    float m0 = b0, m1 = b1, m2 = b2;
+                    if (wall2 >= 0) {
+                        mhits++;
+                        if (colour) {
+                            const RadRect tr = a.rects[wall2];
+                            float u, v;
+                            view_uv(a.hits[wall2], tr, Q, d2, best, u, v);
+                            tap_colour(s.tiles + a.first_tile[wall2], tr, u, v, bilinear, m0, m1, m2);
+                        }
+                    }
+                    v0 = lerp2(gloss, v0, m0), v1 = lerp2(gloss, v1, m1), v2 = lerp2(gloss, v2, m2);
+                }
+                sum0 += fix8(v0), sum1 += fix8(v1), sum2 += fix8(v2);
+            }
+        }
+        const int64_t o = ((int64_t)c * a.height + y) * a.width + x;
+        if (colour) {
+            const int half = 128 * S * S, den = 256 * S * S;
+            uint8_t *p = a.rgb_out + 3 * o;
+            p[0] = (uint8_t)((sum0 + half) / den);
+            p[1] = (uint8_t)((sum1 + half) / den);
+            p[2] = (uint8_t)((sum2 + half) / den);
+        }
+        if (s.cov_out) s.cov_out[o] = (uint8_t)cov;
+    }
+    /* a.tests counts both walks; the three counters are the mirror rays' own */
+    const unsigned long long mt = wave_sum(mtests), n = wave_sum(tests) + mt,
+                             rh = wave_sum(((unsigned long long)mrays << 32) | mhits);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
+    if (lane == 0 && rh) {
+        atomicAdd(ga.g.counters, rh >> 32);
+        if (rh & 0xFFFFFFFFull) atomicAdd(ga.g.counters + 1, rh & 0xFFFFFFFFull);
+        if (mt) atomicAdd(ga.g.counters + 2, mt);
+    }
+}
+
+/*
+ * k_view_trace / k_view_trace_proj with the mirror bounce: the primary records as they write them and, at the same
+ * index of a second plane, a mirror record per sample: tap_record of the wall the mirror ray hit, FMGI_VIEW_MISS
+ * if it hit nothing, FMGI_VIEW_NO_MIRROR for a sample that does not mirror. Nothing here depends on gloss.
+ */
+template <int P>
+__global__ __launch_bounds__(256) void k_view_trace_gloss(TraceGlossArgs ga) {
+    const TraceProjArgs &q = ga.q;
+    const TraceArgs &t = q.t;
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = s.x0 + (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = s.y0 + (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    __shared__ PhiTable phis; /* EQUIRECT only */
+    unsigned long long tests = 0, mtests = 0, hits = 0;
+    unsigned int mrays = 0, mhits = 0;
+    if (x < s.x1 && y < s.y1) {
+        const ViewCam V = a.cams[c];
+        const v3 cam = mk(V.px, V.py, V.pz);
+        const unsigned long long *keys = a.keys + (size_t)c * a.sort_n, *mkeys = ga.g.mkeys + (size_t)c * a.sort_n;
+        const int C = a.counts[c], S = s.samples;
+        const bool bilinear = s.filter != 0;
+        const float px = (float)(x - a.width / 2), py = (float)(y - a.height / 2);
+        if constexpr (P == FMGI_VIEW_EQUIRECT) phi_table(phis, tid, x, S, s.offs, q.kphi);
+        for (int j = 0; j < S; j++) {
+            float fy = 0.0f, st = 0.0f, ct = 0.0f;
+            if constexpr (P == FMGI_VIEW_EQUIRECT) fmgi_sincosf(((float)y + (0.5f + s.offs[j])) * q.ktheta, &st, &ct);
+            else fy = -V.pixel * (py + s.offs[j]);
+            for (int i = 0; i < S; i++) {
+                float fx = 0.0f;
+                float2 phi = make_float2(0.0f, 0.0f);
+                if constexpr (P == FMGI_VIEW_EQUIRECT) phi = phis.sc[i][tid];
+                else fx = V.pixel * (px + s.offs[i]);
+                v3 src, dir;
+                sample_ray<P>(V, cam, fx, fy, phi, st, ct, src, dir);
+                float dist;
+                const int target = view_walk(a, keys, C, src, dir, dist, tests);
+                const int64_t o = record_index(c, S * S, j * S + i, a.height, a.width, y, x);
+                uint4 rec = make_uint4(FMGI_VIEW_MISS, 0u, 0u, 0u), mrec = make_uint4(FMGI_VIEW_NO_MIRROR, 0u, 0u, 0u);
+                if (target >= 0) {
+                    hits++;
+                    const RadRect tr = a.rects[target];
+                    float u, v;
+                    view_uv(a.hits[target], tr, src, dir, dist, u, v);
+                    rec = tap_record((uint32_t)a.first_tile[target], tr, u, v, bilinear);
+                    const v3 Pt = add(src, mul(dir, dist));
+                    if (mirrors(Pt)) {
+                        v3 Q, d2;
+                        float best;
+                        const int wall2 = mirror_walk(a, mkeys, cam, a.hits[target], Pt, dir, Q, d2, best, mtests);
+                        mrays++;
+                        mrec.x = FMGI_VIEW_MISS;
+                        if (wall2 >= 0) {
+                            mhits++;
+                            const RadRect mr = a.rects[wall2];
+                            view_uv(a.hits[wall2], mr, Q, d2, best, u, v);
+                            mrec = tap_record((uint32_t)a.first_tile[wall2], mr, u, v, bilinear);
+                        }
+                    }
+                }
+                if (bilinear) {
+                    ((uint4 *)t.records)[o] = rec;
+                    ((uint4 *)ga.mrecords)[o] = mrec;
+                } else {
+                    ((uint32_t *)t.records)[o] = rec.x;
+                    ((uint32_t *)ga.mrecords)[o] = mrec.x;
+                }
+            }
+        }
+    }
+    const unsigned long long mt = wave_sum(mtests), n = wave_sum(tests) + mt, h = wave_sum(hits),
+                             rh = wave_sum(((unsigned long long)mrays << 32) | mhits);
+    if (lane == 0 && n) atomicAdd(a.tests, n);
+    if (lane == 0 && h) atomicAdd(t.hits, h);
+    if (lane == 0 && rh) {
+        atomicAdd(ga.g.counters, rh >> 32);
+        if (rh & 0xFFFFFFFFull) atomicAdd(ga.g.counters + 1, rh & 0xFFFFFFFFull);
+        if (mt) atomicAdd(ga.g.counters + 2, mt);
+    }
+}
+
+/* a record's colour from one tile set, before fix8: k_view_resolve's gather */
+template <bool BILINEAR>
+__device__ __forceinline__ void record_colour(const uint32_t *T, uint32_t t00, uint32_t dx, uint32_t t10, float fu, float fv,
+                                              float &c0, float &c1, float &c2) {
+    if constexpr (BILINEAR) {
+        const uint32_t w00 = T[t00], w01 = T[t00 + dx], w10 = T[t10], w11 = T[t10 + dx];
+#define FMGI_CH(sh)                                                                                        \
+    lerp2(fv, lerp2(fu, (float)((w00 >> sh) & 255), (float)((w01 >> sh) & 255)),                         \
+          lerp2(fu, (float)((w10 >> sh) & 255), (float)((w11 >> sh) & 255)))
+        c0 = FMGI_CH(0), c1 = FMGI_CH(8), c2 = FMGI_CH(16);
+#undef FMGI_CH
+    } else {
+        const uint32_t w = T[t00];
+        c0 = (float)(w & 255), c1 = (float)((w >> 8) & 255), c2 = (float)((w >> 16) & 255);
+    }
+}
+
+/*
+ * k_view_resolve with the mirror records: per sample both records are read once, every tile set gathers the
+ * primary colour and, for a sample that mirrors, the mirror colour (or the background), blends them with gloss
+ * and adds k_view_shade_gloss's fixed-point colour to its sums.
+ */
+template <bool BILINEAR>
+__global__ __launch_bounds__(256) void k_view_resolve_gloss(ResolveGlossArgs ga) {
+    const ResolveArgs &r = ga.r;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = (int)blockIdx.x * FMGI_VIEW_BLOCK + (wave & 1) * FMGI_VIEW_TILE + (lane & (FMGI_VIEW_TILE - 1));
+    const int y = (int)blockIdx.y * FMGI_VIEW_BLOCK + (wave >> 1) * FMGI_VIEW_TILE + lane / FMGI_VIEW_TILE;
+    const int c = blockIdx.z;
+    if (x >= r.width || y >= r.height) return;
+    const int spp = r.samples * r.samples;
+    const float gloss = ga.gloss;
+    const float b0 = (float)(r.background & 255), b1 = (float)((r.background >> 8) & 255),
+                b2 = (float)((r.background >> 16) & 255);
+    const int bg0 = fix8(b0), bg1 = fix8(b1), bg2 = fix8(b2);
+    int sum0[FMGI_VIEW_SETS], sum1[FMGI_VIEW_SETS], sum2[FMGI_VIEW_SETS], cov = 0;
+#pragma unroll
+    for (int k = 0; k < FMGI_VIEW_SETS; k++) sum0[k] = sum1[k] = sum2[k] = 0;
+    for (int n = 0; n < spp; n++) {
+        const int64_t o = record_index(c, spp, n, r.height, r.width, y, x);
+        typedef uint32_t rec4 __attribute__((ext_vector_type(4)));
+        rec4 rec = {0u, 0u, 0u, 0u}, mrec = {0u, 0u, 0u, 0u};
+        if constexpr (BILINEAR) {
+            rec = ((const rec4 *)r.records)[o];
+            mrec = ((const rec4 *)ga.mrecords)[o];
+        } else {
+            rec.x = ((const uint32_t *)r.records)[o];
+            mrec.x = ((const uint32_t *)ga.mrecords)[o];
+        }
+        const bool hit = rec.x != FMGI_VIEW_MISS, mirror = mrec.x != FMGI_VIEW_NO_MIRROR, mhit = mrec.x != FMGI_VIEW_MISS;
+        cov += hit;
+        const uint32_t t00 = BILINEAR ? rec.x & 0x7FFFFFFFu : rec.x, dx = BILINEAR ? rec.x >> 31 : 0u, t10 = rec.y;
+        const uint32_t m00 = BILINEAR ? mrec.x & 0x7FFFFFFFu : mrec.x, mdx = BILINEAR ? mrec.x >> 31 : 0u, m10 = mrec.y;
+        const float fu = __uint_as_float(rec.z), fv = __uint_as_float(rec.w);
+        const float mfu = __uint_as_float(mrec.z), mfv = __uint_as_float(mrec.w);
+#pragma unroll
+        for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+            if (k >= r.nsets) break;
+            if (!hit) {
+                sum0[k] += bg0, sum1[k] += bg1, sum2[k] += bg2;
+                continue;
+            }
+            float v0, v1, v2;
+            record_colour<BILINEAR>(r.tiles[k], t00, dx, t10, fu, fv, v0, v1, v2);
+            if (mirror) {
+                float m0 = b0, m1 = b1, m2 = b2;
+                if (mhit) record_colour<BILINEAR>(r.tiles[k], m00, mdx, m10, mfu, mfv, m0, m1, m2);
+                v0 = lerp2(gloss, v0, m0), v1 = lerp2(gloss, v1, m1), v2 = lerp2(gloss, v2, m2);
+            }
+            sum0[k] += fix8(v0), sum1[k] += fix8(v1), sum2[k] += fix8(v2);
+        }
+    }
+    const int64_t o = ((int64_t)c * r.height + y) * r.width + x;
+    const int half = 128 * spp, den = 256 * spp;
+#pragma unroll
+    for (int k = 0; k < FMGI_VIEW_SETS; k++) {
+        if (k >= r.nsets) break;
+        uint8_t *q = r.rgb[k] + 3 * o;
+        q[0] = (uint8_t)((sum0[k] + half) / den);
+        q[1] = (uint8_t)((sum1[k] + half) / den);
+        q[2] = (uint8_t)((sum2[k] + half) / den);
+    }
+    if (r.cov_out) r.cov_out[o] = (uint8_t)cov;
+}
+
 bool bad_sort(const ViewArgs &a) {
     return a.sort_n < 2 || a.sort_n > FMGI_RAD_MAX_SORT || (a.sort_n & (a.sort_n - 1)) || a.nrects > a.sort_n;
 }
@@ -749,5 +1113,75 @@ hipError_t fmgi_view_launch_resolve(const ResolveArgs &r, hipStream_t st) {
                     (unsigned)((r.height + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)r.ncams);
     if (r.filter) hipLaunchKernelGGL(k_view_resolve<true>, grid, dim3(256), 0, st, r);
     else hipLaunchKernelGGL(k_view_resolve<false>, grid, dim3(256), 0, st, r);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_candidates_mirror(const ViewArgs &a, hipStream_t s) {
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_sort(a)) return hipErrorInvalidValue;
+    hipError_t e = fmgi_set_lds_attr_once<10>((const void *)k_view_candidates_proj<FMGI_VIEW_MIRROR>, FMGI_RAD_MAX_SORT * 8);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_view_candidates_proj<FMGI_VIEW_MIRROR>, dim3((unsigned)a.ncams), dim3(256), (size_t)a.sort_n * 8, s, a);
+    return hipGetLastError();
+}
+
+static bool bad_gloss_proj(int projection) {
+    return projection != FMGI_VIEW_PINHOLE && projection != FMGI_VIEW_ORTHO && projection != FMGI_VIEW_EQUIRECT;
+}
+
+/* what the shade and trace launches check of their windows and shapes */
+static bool bad_window(const ShadeArgs &s) {
+    const ViewArgs &a = s.v;
+    return bad_sort(a) || a.ncams > FMGI_VIEW_MAX_BATCH || a.width < 1 || a.height < 1 || a.width > FMGI_VIEW_MAX_DIM ||
+           a.height > FMGI_VIEW_MAX_DIM || s.samples < 1 || s.samples > FMGI_VIEW_SAMPLES || (s.filter != 0 && s.filter != 1) ||
+           s.x0 < 0 || s.y0 < 0 || s.x1 <= s.x0 || s.y1 <= s.y0 || s.x1 > a.width || s.y1 > a.height;
+}
+
+hipError_t fmgi_view_launch_shade_gloss(const ShadeGlossArgs &g, int projection, hipStream_t st) {
+    const ShadeArgs &s = g.q.s;
+    const ViewArgs &a = s.v;
+    if (bad_gloss_proj(projection)) return hipErrorInvalidValue;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_window(s) || (a.rgb_out && (!s.tiles || !a.first_tile)) || !g.g.mkeys || !g.g.counters || !(g.g.gloss >= 0.0f) ||
+        !(g.g.gloss <= 1.0f))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    if (projection == FMGI_VIEW_PINHOLE) hipLaunchKernelGGL(k_view_shade_gloss<FMGI_VIEW_PINHOLE>, grid, dim3(256), 0, st, g);
+    else if (projection == FMGI_VIEW_ORTHO) hipLaunchKernelGGL(k_view_shade_gloss<FMGI_VIEW_ORTHO>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(k_view_shade_gloss<FMGI_VIEW_EQUIRECT>, grid, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_trace_gloss(const TraceGlossArgs &g, int projection, hipStream_t st) {
+    const TraceArgs &t = g.q.t;
+    const ShadeArgs &s = t.s;
+    const ViewArgs &a = s.v;
+    if (bad_gloss_proj(projection)) return hipErrorInvalidValue;
+    if (a.ncams <= 0) return hipSuccess;
+    if (bad_window(s) || !a.first_tile || !t.records || !t.hits || !g.mrecords || !g.g.mkeys || !g.g.counters)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.x1 - s.x0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((s.y1 - s.y0 + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)a.ncams);
+    if (projection == FMGI_VIEW_PINHOLE) hipLaunchKernelGGL(k_view_trace_gloss<FMGI_VIEW_PINHOLE>, grid, dim3(256), 0, st, g);
+    else if (projection == FMGI_VIEW_ORTHO) hipLaunchKernelGGL(k_view_trace_gloss<FMGI_VIEW_ORTHO>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(k_view_trace_gloss<FMGI_VIEW_EQUIRECT>, grid, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t fmgi_view_launch_resolve_gloss(const ResolveGlossArgs &g, hipStream_t st) {
+    const ResolveArgs &r = g.r;
+    if (r.ncams <= 0) return hipSuccess;
+    if (r.ncams > FMGI_VIEW_MAX_BATCH || r.width < 1 || r.height < 1 || r.width > FMGI_VIEW_MAX_DIM ||
+        r.height > FMGI_VIEW_MAX_DIM || r.samples < 1 || r.samples > FMGI_VIEW_SAMPLES ||
+        (r.filter != 0 && r.filter != 1) || !r.records || !g.mrecords || r.nsets < 1 || r.nsets > FMGI_VIEW_SETS ||
+        !(g.gloss >= 0.0f) || !(g.gloss <= 1.0f))
+        return hipErrorInvalidValue;
+    for (int k = 0; k < r.nsets; k++)
+        if (!r.tiles[k] || !r.rgb[k]) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((r.width + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK),
+                    (unsigned)((r.height + FMGI_VIEW_BLOCK - 1) / FMGI_VIEW_BLOCK), (unsigned)r.ncams);
+    if (r.filter) hipLaunchKernelGGL(k_view_resolve_gloss<true>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(k_view_resolve_gloss<false>, grid, dim3(256), 0, st, g);
     return hipGetLastError();
 }

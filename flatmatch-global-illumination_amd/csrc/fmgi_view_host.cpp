@@ -12,7 +12,9 @@
  * casts the same rays once with k_view_trace and shades device-resident lightmaps with k_output's read-only form
  * and k_view_resolve, asynchronously on the caller's stream. The *_proj entry points pass a projection
  * through the same functions: the pin-hole takes the calls above unchanged, the orthographic and equirectangular
- * cameras get an orthonormal frame in their ViewCam and the _proj instances of the three kernels.
+ * cameras get an orthonormal frame in their ViewCam and the _proj instances of the three kernels. The *_gloss entry
+ * points pass a mirror weight through the same functions: with gloss > 0 (or for create_gloss) they build
+ * the mirror lists and launch the _gloss kernels, with gloss == 0 they are the calls above.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -44,6 +46,7 @@ float length(F3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
 F3 normalized(F3 a) { return mul(a, 1.0f / length(a)); } /* vector3_cl.c:95-101 */
 
 struct fmgi_view_stats g_stats;
+struct fmgi_view_gloss_stats g_gloss; /* of the last gloss call; any other view call zeroes it */
 
 #define VIEWCHK(expr)                                                                                  \
     do {                                                                                               \
@@ -165,6 +168,7 @@ int view_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, in
     for (int i = 0; i < num_cams; i++)
         if ((rc = make_cam(cams[i], vc[(size_t)i], fn)) != FMGI_OK) return rc;
     memset(&g_stats, 0, sizeof g_stats);
+    memset(&g_gloss, 0, sizeof g_gloss);
     if (num_cams == 0) return FMGI_OK;
     if ((rc = no_device()) != FMGI_OK) return rc;
 
@@ -339,6 +343,9 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+/* a mirror weight the gloss calls take: a number in [0, 1] */
+bool bad_gloss(float gloss) { return !(gloss >= 0.0f && gloss <= 1.0f); }
+
 /* rays per k_view_shade launch: FMGI_VIEW_MAX_RAYS, or FMGI_VIEW_RAYS_PER_LAUNCH from the environment (tests
    use it to reach the windowed launches with small images) */
 int64_t shade_ray_budget() {
@@ -349,8 +356,7 @@ int64_t shade_ray_budget() {
 
 int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
               int projection, const uint8_t *tiles_rgb, const uint8_t *background, int samples, int filter, uint8_t *rgb_out,
-              uint8_t *coverage_out) {
-    static const char fn[] = "fmgi_shade_views";
+              uint8_t *coverage_out, float gloss = 0.0f, const char *fn = "fmgi_shade_views") {
     Walls w;
     int rc = check_geometry(geo, w, fn);
     if (rc != FMGI_OK) return rc;
@@ -362,13 +368,16 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
     if (filter != FMGI_VIEW_NEAREST && filter != FMGI_VIEW_BILINEAR) return arg_err(fn, "filter is neither nearest nor bilinear");
     std::vector<ViewCam> vc((size_t)std::max(num_cams, 1));
     if ((rc = make_cams(cams, num_cams, projection, vc, fn)) != FMGI_OK) return rc;
+    if (bad_gloss(gloss)) return arg_err(fn, "gloss is not a number in [0, 1]");
     memset(&g_stats, 0, sizeof g_stats);
+    memset(&g_gloss, 0, sizeof g_gloss);
     if (num_cams == 0) return FMGI_OK;
     if ((rc = no_device()) != FMGI_OK) return rc;
 
+    const bool mirror = gloss > 0.0f; /* gloss == 0 is the call without it: no mirror list, no second walk */
     const int nr = geo->numWalls;
     const int64_t pix = (int64_t)width * height, spp = (int64_t)samples * samples, budget = shade_ray_budget();
-    /* cameras per launch: at most 2^26 pixels of outputs on the device, and at most `budget` rays */
+    /* cameras per launch: at most 2^26 pixels of outputs on the device, and at most `budget` primary rays */
     const int batch = (int)std::max<int64_t>(
         1, std::min<int64_t>({(int64_t)num_cams, FMGI_VIEW_MAX_BATCH, ((int64_t)1 << 26) / pix, budget / (pix * spp)}));
     /* one camera over the budget: windows of whole workgroup rows, then of workgroup columns */
@@ -379,12 +388,13 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
         cols = (int)std::min<int64_t>(width, std::max<int64_t>(B, budget / ((int64_t)rows * spp) / B * B));
     }
     const int64_t ntiles = nr ? w.first_tile[(size_t)nr - 1] + (int64_t)geo->walls[nr - 1].lightmapSetup[1] * geo->walls[nr - 1].lightmapSetup[2] : 0;
-    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_tests, d_rgb, d_cov, d_first, d_tiles;
+    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_tests, d_rgb, d_cov, d_first, d_tiles, d_mkeys, d_mcounts;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<int32_t> counts((size_t)batch);
-    unsigned long long tests = 0;
-    ShadeProjArgs q;
-    memset(&q, 0, sizeof q);
+    unsigned long long tests[4] = {0, 0, 0, 0}; /* tests, then the mirror rays, hits and tests */
+    ShadeGlossArgs gq;
+    memset(&gq, 0, sizeof gq);
+    ShadeProjArgs &q = gq.q;
     ShadeArgs &s = q.s;
     ViewArgs &a = s.v;
     q.kphi = 6.2831855f / (float)width;
@@ -402,8 +412,12 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
     VIEWCHK(d_cams.alloc((size_t)batch * sizeof(ViewCam)));
     VIEWCHK(d_keys.alloc((size_t)batch * w.sort_n * 8));
     VIEWCHK(d_counts.alloc((size_t)batch * 4));
-    VIEWCHK(d_tests.alloc(8));
-    VIEWCHK(hipMemset(d_tests.p, 0, 8));
+    VIEWCHK(d_tests.alloc(32));
+    VIEWCHK(hipMemset(d_tests.p, 0, 32));
+    if (mirror) {
+        VIEWCHK(d_mkeys.alloc((size_t)batch * w.sort_n * 8));
+        VIEWCHK(d_mcounts.alloc((size_t)batch * 4));
+    }
     if (coverage_out) VIEWCHK(d_cov.alloc((size_t)batch * pix));
     if (rgb_out) {
         VIEWCHK(d_rgb.alloc((size_t)batch * pix * 3));
@@ -435,6 +449,9 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
     s.samples = samples;
     s.filter = filter;
     for (int i = 0; i < samples; i++) s.offs[i] = (float)(2 * i + 1 - samples) / (float)(2 * samples);
+    gq.g.mkeys = d_mkeys.as<unsigned long long>();
+    gq.g.counters = d_tests.as<unsigned long long>() + 1;
+    gq.g.gloss = gloss;
     for (int c0 = 0; c0 < num_cams; c0 += batch) {
         const int n = std::min(batch, num_cams - c0);
         const size_t px = (size_t)n * pix, o = (size_t)c0 * pix;
@@ -443,12 +460,19 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
         VIEWCHK(hipEventRecord(ev[1], nullptr));
         if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
         else VIEWCHK(fmgi_view_launch_candidates_proj(a, projection, nullptr));
+        if (mirror) { /* the mirror lists: the same walls and cameras into buffers of their own */
+            ViewArgs m = a;
+            m.keys = d_mkeys.as<unsigned long long>();
+            m.counts = d_mcounts.as<int32_t>();
+            VIEWCHK(fmgi_view_launch_candidates_mirror(m, nullptr));
+        }
         VIEWCHK(hipEventRecord(ev[2], nullptr));
         for (s.y0 = 0; s.y0 < height; s.y0 += rows)
             for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
                 s.y1 = std::min(height, s.y0 + rows);
                 s.x1 = std::min(width, s.x0 + cols);
-                if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_shade(s, nullptr));
+                if (mirror) VIEWCHK(fmgi_view_launch_shade_gloss(gq, projection, nullptr));
+                else if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_shade(s, nullptr));
                 else VIEWCHK(fmgi_view_launch_shade_proj(q, projection, nullptr));
             }
         VIEWCHK(hipEventRecord(ev[3], nullptr));
@@ -465,10 +489,13 @@ int shade_run(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, i
         if (rgb_out) VIEWCHK(hipMemcpy(rgb_out + 3 * o, d_rgb.p, px * 3, hipMemcpyDeviceToHost));
         if (coverage_out) VIEWCHK(hipMemcpy(coverage_out + o, d_cov.p, px, hipMemcpyDeviceToHost));
     }
-    VIEWCHK(hipMemcpy(&tests, d_tests.p, 8, hipMemcpyDeviceToHost));
+    VIEWCHK(hipMemcpy(tests, d_tests.p, 32, hipMemcpyDeviceToHost));
     g_stats.cameras = num_cams;
     g_stats.rays = (int64_t)num_cams * pix * spp;
-    g_stats.tests = (int64_t)tests;
+    g_stats.tests = (int64_t)tests[0];
+    g_gloss.mirror_rays = (int64_t)tests[1];
+    g_gloss.mirror_hits = (int64_t)tests[2];
+    g_gloss.mirror_tests = (int64_t)tests[3];
 done:
     for (auto &e : ev)
         if (e) hipEventDestroy(e);
@@ -487,7 +514,8 @@ struct fmgi_view_cache {
     int projection = FMGI_PROJ_PINHOLE;
     struct fmgi_view_cache_info info;
     std::vector<OutWallIn> walls; /* what the OutWall table is made of; norm follows the call's spa */
-    DevBuf records, out_walls, packed;
+    DevBuf records, mrecords, out_walls, packed; /* mrecords: the mirror records' plane, or none */
+    bool mirror = false;
     int out_spa = -1;        /* the spa out_walls holds, -1: none yet */
     int packed_sets = 0;     /* sets `packed` has room for */
     hipEvent_t ev_tiles = nullptr, ev_shade = nullptr; /* the last launch that reads out_walls / packed */
@@ -516,8 +544,8 @@ int64_t cache_bytes(int num_cams, int width, int height, int samples, int filter
 }
 
 int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height, int projection,
-                 int samples, int filter, fmgi_view_cache **out) {
-    static const char fn[] = "fmgi_view_cache_create";
+                 int samples, int filter, fmgi_view_cache **out, bool mirror = false,
+                 const char *fn = "fmgi_view_cache_create") {
     if (!out) return arg_err(fn, "null out");
     *out = nullptr;
     Walls w;
@@ -548,12 +576,13 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
         cols = (int)std::min<int64_t>(width, std::max<int64_t>(B, budget / ((int64_t)rows * spp) / B * B));
     }
     fmgi_view_cache *v = new fmgi_view_cache;
-    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_counters, d_first;
+    DevBuf d_rects, d_hits, d_cams, d_keys, d_counts, d_counters, d_first, d_mkeys, d_mcounts;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    unsigned long long counters[2] = {0, 0};
+    unsigned long long counters[5] = {0, 0, 0, 0, 0}; /* tests, hits, then the mirror rays, hits and tests */
     float ms = 0;
-    TraceProjArgs q;
-    memset(&q, 0, sizeof q);
+    TraceGlossArgs gq;
+    memset(&gq, 0, sizeof gq);
+    TraceProjArgs &q = gq.q;
     TraceArgs &t = q.t;
     ShadeArgs &s = t.s;
     ViewArgs &a = s.v;
@@ -569,9 +598,12 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     v->info.cameras = num_cams, v->info.width = width, v->info.height = height, v->info.samples = samples;
     v->info.filter = filter, v->info.num_texels = geo->numTexels, v->info.tiles = ntiles;
     v->info.rays = (int64_t)num_cams * pix * spp;
-    v->info.bytes = cache_bytes(num_cams, width, height, samples, filter);
+    v->info.bytes = cache_bytes(num_cams, width, height, samples, filter) * (mirror ? 2 : 1);
     v->walls = ow;
-    VIEWCHK(v->records.alloc((size_t)v->info.bytes));
+    v->mirror = mirror;
+    memset(&g_gloss, 0, sizeof g_gloss);
+    VIEWCHK(v->records.alloc((size_t)cache_bytes(num_cams, width, height, samples, filter)));
+    if (mirror) VIEWCHK(v->mrecords.alloc((size_t)cache_bytes(num_cams, width, height, samples, filter)));
     VIEWCHK(v->out_walls.alloc((size_t)std::max(nr, 1) * sizeof(OutWall)));
     VIEWCHK(hipEventCreateWithFlags(&v->ev_tiles, hipEventDisableTiming));
     VIEWCHK(hipEventCreateWithFlags(&v->ev_shade, hipEventDisableTiming));
@@ -586,8 +618,12 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     VIEWCHK(hipMemcpy(d_cams.p, vc.data(), (size_t)num_cams * sizeof(ViewCam), hipMemcpyHostToDevice));
     VIEWCHK(d_keys.alloc((size_t)num_cams * w.sort_n * 8));
     VIEWCHK(d_counts.alloc((size_t)num_cams * 4));
-    VIEWCHK(d_counters.alloc(16));
-    VIEWCHK(hipMemset(d_counters.p, 0, 16));
+    VIEWCHK(d_counters.alloc(40));
+    VIEWCHK(hipMemset(d_counters.p, 0, 40));
+    if (mirror) {
+        VIEWCHK(d_mkeys.alloc((size_t)num_cams * w.sort_n * 8));
+        VIEWCHK(d_mcounts.alloc((size_t)num_cams * 4));
+    }
     a.rects = d_rects.as<RadRect>();
     a.hits = d_hits.as<AoRect>();
     a.nrects = nr;
@@ -608,6 +644,13 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     VIEWCHK(hipEventRecord(ev[0], nullptr));
     if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_candidates(a, nullptr));
     else VIEWCHK(fmgi_view_launch_candidates_proj(a, projection, nullptr));
+    if (mirror) {
+        ViewArgs m = a;
+        m.keys = d_mkeys.as<unsigned long long>();
+        m.counts = d_mcounts.as<int32_t>();
+        VIEWCHK(fmgi_view_launch_candidates_mirror(m, nullptr));
+    }
+    gq.g.counters = d_counters.as<unsigned long long>() + 2;
     VIEWCHK(hipEventRecord(ev[1], nullptr));
     for (int c0 = 0; c0 < num_cams; c0 += batch) {
         a.ncams = std::min(batch, num_cams - c0);
@@ -615,11 +658,14 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
         a.keys = d_keys.as<unsigned long long>() + (size_t)c0 * w.sort_n;
         a.counts = d_counts.as<int32_t>() + c0;
         t.records = v->records.as<char>() + (size_t)c0 * spp * pix * rec;
+        gq.mrecords = mirror ? v->mrecords.as<char>() + (size_t)c0 * spp * pix * rec : nullptr;
+        gq.g.mkeys = mirror ? d_mkeys.as<unsigned long long>() + (size_t)c0 * w.sort_n : nullptr;
         for (s.y0 = 0; s.y0 < height; s.y0 += rows)
             for (s.x0 = 0; s.x0 < width; s.x0 += cols) {
                 s.y1 = std::min(height, s.y0 + rows);
                 s.x1 = std::min(width, s.x0 + cols);
-                if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_trace(t, nullptr));
+                if (mirror) VIEWCHK(fmgi_view_launch_trace_gloss(gq, projection, nullptr));
+                else if (projection == FMGI_PROJ_PINHOLE) VIEWCHK(fmgi_view_launch_trace(t, nullptr));
                 else VIEWCHK(fmgi_view_launch_trace_proj(q, projection, nullptr));
             }
     }
@@ -629,9 +675,12 @@ int cache_create(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams
     v->info.cand_ms = ms;
     VIEWCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
     v->info.trace_ms = ms;
-    VIEWCHK(hipMemcpy(counters, d_counters.p, 16, hipMemcpyDeviceToHost));
+    VIEWCHK(hipMemcpy(counters, d_counters.p, 40, hipMemcpyDeviceToHost));
     v->info.tests = (int64_t)counters[0];
     v->info.hits = (int64_t)counters[1];
+    g_gloss.mirror_rays = (int64_t)counters[2];
+    g_gloss.mirror_hits = (int64_t)counters[3];
+    g_gloss.mirror_tests = (int64_t)counters[4];
     *out = v;
     v = nullptr;
 done:
@@ -682,17 +731,26 @@ done:
 }
 
 int cache_shade(fmgi_view_cache *v, const void *const *tiles_dev, int num_sets, const uint8_t *background,
-                void *const *rgb_dev, void *coverage_dev, hipStream_t st) {
-    static const char fn[] = "fmgi_view_cache_shade";
+                void *const *rgb_dev, void *coverage_dev, hipStream_t st, float gloss = 0.0f,
+                const char *fn = "fmgi_view_cache_shade") {
     if (!v || !tiles_dev || !rgb_dev || !background) return arg_err(fn, "null argument");
     if (num_sets < 1) return arg_err(fn, "num_sets < 1");
     for (int k = 0; k < num_sets; k++)
         if (!tiles_dev[k] || !rgb_dev[k]) return arg_err(fn, "null set");
+    if (bad_gloss(gloss)) return arg_err(fn, "gloss is not a number in [0, 1]");
+    if (gloss > 0.0f && !v->mirror) {
+        char b[160];
+        snprintf(b, sizeof b, "%s: gloss > 0 on a traced view without mirror records (fmgi_view_cache_create_gloss makes them)", fn);
+        return internal_set_err(FMGI_ERR_STATE, b);
+    }
     int rc = FMGI_OK;
     const int64_t ntiles = v->info.tiles;
     const int per_pass = std::min(num_sets, FMGI_VIEW_SETS);
-    ResolveArgs r;
-    memset(&r, 0, sizeof r);
+    ResolveGlossArgs gr;
+    memset(&gr, 0, sizeof gr);
+    ResolveArgs &r = gr.r;
+    gr.mrecords = v->mrecords.p;
+    gr.gloss = gloss;
     VIEWCHK(hipSetDevice(v->device));
     if (v->packed_sets < per_pass) { /* grow the scratch once nothing reads it any more */
         if (v->shade_pending) VIEWCHK(hipEventSynchronize(v->ev_shade));
@@ -725,7 +783,9 @@ int cache_shade(fmgi_view_cache *v, const void *const *tiles_dev, int num_sets, 
             r.rgb[k] = (uint8_t *)rgb_dev[k0 + k];
         }
         r.cov_out = k0 == 0 ? (uint8_t *)coverage_dev : nullptr;
-        VIEWCHK(fmgi_view_launch_resolve(r, st));
+        /* gloss == 0 is the plain picture, through the plain kernel */
+        if (gloss > 0.0f) VIEWCHK(fmgi_view_launch_resolve_gloss(gr, st));
+        else VIEWCHK(fmgi_view_launch_resolve(r, st));
     }
     VIEWCHK(hipEventRecord(v->ev_shade, st));
     v->shade_pending = true;
@@ -748,6 +808,37 @@ FMGI_API int fmgi_view_cache_create(const fmgi_geometry *geo, const fmgi_camera 
 FMGI_API int fmgi_view_cache_create_proj(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
                                          int height, int projection, int samples, int filter, fmgi_view_cache **out) {
     return cache_create(geo, cams, num_cams, width, height, projection, samples, filter, out);
+}
+
+FMGI_API int fmgi_view_cache_create_gloss(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
+                                          int height, int projection, int samples, int filter, fmgi_view_cache **out) {
+    return cache_create(geo, cams, num_cams, width, height, projection, samples, filter, out, true,
+                        "fmgi_view_cache_create_gloss");
+}
+
+FMGI_API int fmgi_view_cache_has_mirror(const fmgi_view_cache *vc) {
+    if (!vc) return arg_err("fmgi_view_cache_has_mirror", "null argument");
+    return vc->mirror ? 1 : 0;
+}
+
+FMGI_API int fmgi_view_cache_shade_gloss(const fmgi_view_cache *vc, const void *const *tiles_dev, int num_sets,
+                                         const uint8_t background[3], float gloss, void *const *rgb_dev,
+                                         void *coverage_dev, void *stream) {
+    return cache_shade(const_cast<fmgi_view_cache *>(vc), tiles_dev, num_sets, background, rgb_dev, coverage_dev,
+                       (hipStream_t)stream, gloss, "fmgi_view_cache_shade_gloss");
+}
+
+FMGI_API int fmgi_shade_views_gloss(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                                    int projection, const uint8_t *tiles_rgb, const uint8_t background[3], int samples,
+                                    int filter, float gloss, uint8_t *rgb_out, uint8_t *coverage_out) {
+    return shade_run(geo, cams, num_cams, width, height, projection, tiles_rgb, background, samples, filter, rgb_out,
+                     coverage_out, gloss, "fmgi_shade_views_gloss");
+}
+
+FMGI_API int fmgi_view_gloss_stats(struct fmgi_view_gloss_stats *out) {
+    if (!out) return internal_set_err(FMGI_ERR_ARG, "null stats");
+    *out = g_gloss;
+    return FMGI_OK;
 }
 
 FMGI_API int fmgi_view_cache_projection(const fmgi_view_cache *vc) {

@@ -23,7 +23,7 @@ HOST_ONLY = -1  # FMGI_HOST_ONLY: a context without a device (scene checks and p
 from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM, KERNEL_AUTO, KERNEL_EXACT, KERNEL_FAST, KERNEL_GRID, KERNEL_HYBRID, RadStats, Timing, FmgiError, Geometry, Stats,
                    COLOUR_STATE_COUNT, RECOLOUR_MAX_SCENARIOS, Palette, FILTER_MAX_MAPS, FILTER_MAX_RADIUS,
                    SPARSE_COUNT_BITS, SparseInfo, BakeSparseStats,
-                   VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewStats, check,
+                   VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewGlossStats, ViewStats, check,
                    PROJ_EQUIRECT, PROJ_ORTHO, PROJ_PINHOLE,
                    RAD_CACHE_MAX_ITERATIONS, RAD_CACHE_MAX_SETS, RadCacheInfo,
                    load)
@@ -65,6 +65,7 @@ __all__ = [
     "shade_views",
     "view_candidates",
     "view_stats",
+    "view_gloss_stats",
     "ViewCache",
     "view_cache_bytes",
     "VIEW_CACHE_MAX_SETS",
@@ -923,14 +924,16 @@ def _projection(projection) -> int:
 
 
 def shade_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray | None = None, background=(0, 0, 0),
-                samples: int = 1, filter: str = "nearest", *, projection: str = "pinhole") -> dict:
+                samples: int = 1, filter: str = "nearest", *, projection: str = "pinhole", gloss: float = 0.0) -> dict:
     """Supersampled, filtered camera views (fmgi_shade_views): samples x samples rays per pixel, each coloured
     from the hit wall's tiles ("nearest": the tile it lands in, "bilinear": the four around it, clamped to the
     wall) or `background`, averaged in fixed point. Returns {"coverage"} (uint8 [cameras, height, width]: the
     pixel's rays that hit a wall) and, when tiles_rgb is given, {"rgb"} (uint8, a trailing [3]). samples=1 with
     "nearest" gives render_views' rgb. projection: "pinhole", "ortho" (parallel rays along dir, `pixel` metres
     per pixel: the plan at true scale) or "equirect" (the 360-degree panorama from pos, column width / 2 looking
-    along dir; fmgi_shade_views_proj)."""
+    along dir; fmgi_shade_views_proj). gloss in [0, 1]: a sample that lands on the floor (z <= 0.0005, where the
+    bake mirrors its photons) casts one mirror ray and takes gloss of its colour from what that ray sees
+    (fmgi_shade_views_gloss); 0 is the matt floor of the calls above."""
     lib = load()
     if filter not in _VIEW_FILTERS:
         raise FmgiError(f"filter {filter!r}: one of {sorted(_VIEW_FILTERS)}")
@@ -947,7 +950,12 @@ def shade_views(sc: Scene, cams, width: int, height: int, tiles_rgb: np.ndarray 
     bg = np.array(background, np.uint8)
     assert bg.shape == (3,)
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    if proj == PROJ_PINHOLE:
+    if gloss != 0:
+        check(lib.fmgi_shade_views_gloss(C.byref(g), p(cams), n, width, height, proj,
+                                         None if tiles is None else p(tiles), p(bg), samples, _VIEW_FILTERS[filter],
+                                         gloss, p(out["rgb"]) if tiles is not None else None, p(out["coverage"])),
+              "fmgi_shade_views_gloss")
+    elif proj == PROJ_PINHOLE:
         check(lib.fmgi_shade_views(C.byref(g), p(cams), n, width, height, None if tiles is None else p(tiles), p(bg),
                                    samples, _VIEW_FILTERS[filter], p(out["rgb"]) if tiles is not None else None,
                                    p(out["coverage"])), "fmgi_shade_views")
@@ -989,6 +997,14 @@ def view_stats() -> dict:
     return st.as_dict()
 
 
+def view_gloss_stats() -> dict:
+    """fmgi_view_gloss_stats: the mirror rays, their hits and their intersects() tests of the last shade_views call
+    with gloss > 0 or ViewCache(mirror=True); zeros after any other view call."""
+    st = ViewGlossStats()
+    check(load().fmgi_view_gloss_stats(C.byref(st)), "fmgi_view_gloss_stats")
+    return st.as_dict()
+
+
 # ---- traced views (include/flatmatch_gi.h, DESIGN §16) ------------------------------------------------
 
 def view_cache_bytes(num_cams: int, width: int, height: int, samples: int = 1, filter: str = "nearest") -> int:
@@ -1006,10 +1022,12 @@ def _ptr_array(ptrs):
 class ViewCache:
     """A traced view (fmgi_view_cache): shade_views' rays cast once, every sample's taps kept on the device.
     tiles() runs the output step on device lightmaps and shade() gathers one picture per tile set, each what
-    output_tiles followed by shade_views gives, with no host round trip. Device buffers are integer addresses."""
+    output_tiles followed by shade_views gives, with no host round trip. Device buffers are integer addresses.
+    mirror=True also traces every floor sample's mirror ray (fmgi_view_cache_create_gloss), so that shade() takes
+    any gloss from the one trace."""
 
     def __init__(self, sc: Scene, cams, width: int, height: int, samples: int = 1, filter: str = "nearest", *,
-                 projection: str = "pinhole"):
+                 projection: str = "pinhole", mirror: bool = False):
         self.lib = load()
         self.h = None
         if filter not in _VIEW_FILTERS:
@@ -1018,7 +1036,11 @@ class ViewCache:
         cams = _cameras(cams)
         g, keep = make_geometry(sc, np.zeros((max(sc.num_texels, 1), 4), np.float32))
         h = C.c_void_p()
-        if proj == PROJ_PINHOLE:
+        if mirror:
+            check(self.lib.fmgi_view_cache_create_gloss(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width,
+                                                        height, proj, samples, _VIEW_FILTERS[filter], C.byref(h)),
+                  "fmgi_view_cache_create_gloss")
+        elif proj == PROJ_PINHOLE:
             check(self.lib.fmgi_view_cache_create(C.byref(g), cams.ctypes.data_as(C.c_void_p), len(cams), width, height,
                                                   samples, _VIEW_FILTERS[filter], C.byref(h)), "fmgi_view_cache_create")
         else:
@@ -1033,6 +1055,11 @@ class ViewCache:
         """the camera model the view was traced with: "pinhole", "ortho" or "equirect" """
         code = check(self.lib.fmgi_view_cache_projection(self.h), "fmgi_view_cache_projection")
         return {v: k for k, v in PROJECTIONS.items()}[code]
+
+    @property
+    def has_mirror(self) -> bool:
+        """whether the view holds mirror records (mirror=True)"""
+        return bool(check(self.lib.fmgi_view_cache_has_mirror(self.h), "fmgi_view_cache_has_mirror"))
 
     def close(self):
         if self.h:
@@ -1061,16 +1088,22 @@ class ViewCache:
         check(self.lib.fmgi_view_cache_tiles(self.h, tp, n, spa, tint_extra, op, C.c_void_p(stream or None)),
               "fmgi_view_cache_tiles")
 
-    def shade(self, tile_ptrs, rgb_ptrs, background=(0, 0, 0), coverage_ptr: int = 0, stream: int = 0):
+    def shade(self, tile_ptrs, rgb_ptrs, background=(0, 0, 0), coverage_ptr: int = 0, stream: int = 0, *,
+              gloss: float = 0.0):
         """fmgi_view_cache_shade: rgb_ptrs[k] (uint8 [cameras][height][width][3]) = shade_views' rgb for the device
         tiles at tile_ptrs[k]; coverage_ptr (uint8 [cameras][height][width], or 0) = its coverage. Asynchronous on
-        `stream`."""
+        `stream`. gloss > 0 (fmgi_view_cache_shade_gloss) needs a view made with mirror=True."""
         tp, n = _ptr_array(tile_ptrs)
         rp, m = _ptr_array(rgb_ptrs)
         if n != m:
             raise FmgiError(f"shade: {n} tile buffers for {m} pictures")
         bg = np.array(background, np.uint8)
         assert bg.shape == (3,)
+        if gloss != 0:
+            check(self.lib.fmgi_view_cache_shade_gloss(self.h, tp, n, bg.ctypes.data_as(C.c_void_p), gloss, rp,
+                                                       C.c_void_p(coverage_ptr or None), C.c_void_p(stream or None)),
+                  "fmgi_view_cache_shade_gloss")
+            return
         check(self.lib.fmgi_view_cache_shade(self.h, tp, n, bg.ctypes.data_as(C.c_void_p), rp,
                                              C.c_void_p(coverage_ptr or None), C.c_void_p(stream or None)),
               "fmgi_view_cache_shade")

@@ -87,6 +87,11 @@ EXPORTS = (
     "fmgi_view_candidates_proj",
     "fmgi_view_cache_create_proj",
     "fmgi_view_cache_projection",
+    "fmgi_shade_views_gloss",
+    "fmgi_view_gloss_stats",
+    "fmgi_view_cache_create_gloss",
+    "fmgi_view_cache_shade_gloss",
+    "fmgi_view_cache_has_mirror",
     "fmgi_palette_reference",
     "fmgi_palette_table",
     "fmgi_states_bytes",
@@ -228,6 +233,15 @@ class ViewStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ViewGlossStats(C.Structure):
+    """struct fmgi_view_gloss_stats (include/flatmatch_gi.h)."""
+
+    _fields_ = [("mirror_rays", C.c_int64), ("mirror_hits", C.c_int64), ("mirror_tests", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class ViewCacheInfo(C.Structure):
@@ -442,6 +456,13 @@ def load() -> C.CDLL:
         "fmgi_view_cache_create_proj": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.POINTER(vp)]),
         "fmgi_view_cache_projection": (C.c_int, [vp]),
+        "fmgi_shade_views_gloss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int,
+                                             C.c_float, vp, vp]),
+        "fmgi_view_gloss_stats": (C.c_int, [C.POINTER(ViewGlossStats)]),
+        "fmgi_view_cache_create_gloss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(vp)]),
+        "fmgi_view_cache_shade_gloss": (C.c_int, [vp, vp, C.c_int, vp, C.c_float, vp, vp, vp]),
+        "fmgi_view_cache_has_mirror": (C.c_int, [vp]),
         "fmgi_palette_reference": (None, [C.POINTER(Palette)]),
         "fmgi_palette_table": (C.c_int, [C.POINTER(Palette), vp]),
         "fmgi_states_bytes": (C.c_size_t, [C.c_int]),

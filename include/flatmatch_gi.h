@@ -311,6 +311,54 @@ int fmgi_view_cache_create_proj(const fmgi_geometry *geo, const fmgi_camera *cam
 /* the projection a traced view was made with (FMGI_PROJ_*), or FMGI_ERR_ARG for a NULL handle */
 int fmgi_view_cache_projection(const fmgi_view_cache *vc);
 
+/* The glossy floor: the bake mirrors a photon that lands at z <= 0.0005 three times out of four, and
+   these calls draw that floor with one mirror bounce. Everything up to a sample's primary hit is
+   fmgi_shade_views_proj's: origin src, direction dir, wall t with normal n_t, distance dist, colour val[c] (the
+   tap before its fixed-point step). All arithmetic is fp32 in this order, no FMA:
+     mirror sample  the sample hit a wall and !(P.z > 4.99999965541064739227294921875e-4f), P = src + dir * dist
+                    (the bake's test; no test on the wall's orientation)
+     mirror ray     two = 2 * dot(n_t, dir), d2 = dir - n_t * two (not normalised again), Q = P + d2 * 1e-5f
+     mirror list    per camera every wall of the scene, no culls, keyed by its shortest distance to the camera
+                    position and sorted by (key bits, wall index); the same list for all three projections
+     mirror walk    best = inf, wall2 = -1, base = |Q - pos|; for the list's entries in order: stop if
+                    (base + best) < key; count one test; dn = intersects(wall, Q, d2, best); skip if dn < 0;
+                    if dn <= best take the wall and best = dn
+     colour         mval[c] = background[c] if wall2 < 0, else wall2's tap at Q + d2 * best (nearest or bilinear
+                    as the call's filter says); the sample's colour is (1 - gloss) * val[c] + gloss * mval[c], then
+                    the fixed-point step and the resolve of fmgi_shade_views. One bounce: the mirror hit is not
+                    reflected again. Samples that do not mirror keep val.
+   Coverage stays the number of primary hits. fmgi_view_stats.rays stays the primary rays, .tests counts both
+   walks; the second walk runs whether or not rgb_out is given. gloss == 0 is fmgi_shade_views_proj: same
+   launches, bytes and tests, no mirror list and no second walk.
+   Argument errors: those of fmgi_shade_views_proj in its order, then a gloss that is NaN, infinite, below 0 or
+   above 1 (FMGI_ERR_ARG before any device call), then FMGI_ERR_NO_DEVICE. */
+int fmgi_shade_views_gloss(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width, int height,
+                           int projection, const uint8_t *tiles_rgb, const uint8_t background[3], int samples,
+                           int filter, float gloss, uint8_t *rgb_out, uint8_t *coverage_out);
+/* the mirror rays of the last fmgi_shade_views_gloss (gloss > 0) or fmgi_view_cache_create_gloss call, how many of
+   them hit a wall and their intersects() evaluations; zeros after any other render, shade or create call */
+struct fmgi_view_gloss_stats {
+    int64_t mirror_rays, mirror_hits, mirror_tests;
+};
+int fmgi_view_gloss_stats(struct fmgi_view_gloss_stats *out);
+/* A traced view with mirror records: fmgi_view_cache_create_proj's checks, trace and primary records, and in a
+   second allocation, at the same [c][n][y][x] index and in the same NEAREST / BILINEAR form, one mirror record
+   per sample (first word 0xFFFFFFFE: the sample does not mirror, 0xFFFFFFFF: its mirror ray missed). The records do
+   not depend on gloss. info.bytes covers both planes (twice fmgi_view_cache_bytes), info.tests is the sum of both
+   walks (== fmgi_view_stats.tests of the matching fmgi_shade_views_gloss call), info.hits the primary hits.
+   FMGI_ERR_OOM leaves nothing allocated. */
+int fmgi_view_cache_create_gloss(const fmgi_geometry *geo, const fmgi_camera *cams, int num_cams, int width,
+                                 int height, int projection, int samples, int filter, fmgi_view_cache **out);
+/* fmgi_view_cache_shade with the mirror bounce: rgb_dev[k] = fmgi_shade_views_gloss' rgb_out for tiles_dev[k] and
+   this gloss, from one trace for every lightmap and every gloss. gloss == 0 (and fmgi_view_cache_shade on such a
+   view) is the plain picture. Errors: fmgi_view_cache_shade's, then a gloss outside [0, 1] or NaN (FMGI_ERR_ARG),
+   then gloss > 0 on a view without mirror records (FMGI_ERR_STATE), all before any device call. */
+int fmgi_view_cache_shade_gloss(const fmgi_view_cache *vc, const void *const *tiles_dev, int num_sets,
+                                const uint8_t background[3], float gloss, void *const *rgb_dev, void *coverage_dev,
+                                void *stream);
+/* 1 if the traced view holds mirror records, 0 if not, FMGI_ERR_ARG for a NULL handle */
+int fmgi_view_cache_has_mirror(const fmgi_view_cache *vc);
+
 /* ---- Build-defined device-resident API ---------------------------------------------------------- */
 enum {
     FMGI_OK = 0,

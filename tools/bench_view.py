@@ -22,6 +22,15 @@ on the whole scene, equirect stands at the case's camera position.
 
   python tools/bench_view.py --projection equirect --width 2048 --height 1024
   python tools/bench_view.py --projection ortho --width 2048 --height 1536
+
+With --gloss G the tool times the glossy floor: k_view_shade_gloss at gloss G against k_view_shade (gloss
+0) of the same process, arms alternating, best of --rounds after two warm-up rounds, on the two cases and on a
+camera that looks straight down at box200's floor so that every sample mirrors. It prints the mirror rays, the
+mirror tests and tests per mirror ray, the time the second walk adds per mirror test against k_view_shade's time
+per test on box2000, and for a traced view the trace with and without mirror records and shade per picture
+with and without gloss.
+
+  python tools/bench_view.py --gloss 0.75 --width 1024 --height 768 --rounds 5
 """
 import argparse
 import json
@@ -109,10 +118,91 @@ def projection_main(a):
         print(json.dumps(res), flush=True)
 
 
+# box200 from 2.5 m above its 10 m x 8 m floor, looking straight down: the screen plane is 1 m away, so a span of
+# 2.048 m covers 5.12 m x 3.84 m of floor at 4 : 3; the image stays on the floor and every sample mirrors
+FLOOR_CASE = ("box200", dict(pos=(5, 4, 2.5), dir=(0, 0, -1), up=(0, 1, 0)), 0.002 * 1024)
+
+
+def gloss_main(a):
+    """k_view_shade_gloss against k_view_shade, arms alternating in one process; then the traced view"""
+    import torch
+
+    import fmgi
+
+    W, H, S, G = a.width, a.height, a.samples, a.gloss
+    cases = {name: (sname, cam, pixel * 4096) for name, (sname, _, cam, pixel) in CASES.items()}
+    cases["box200_floor"] = FLOOR_CASE
+    per_test = {}
+    for name, (sname, cam, span) in cases.items():
+        sc = load_scene(sname)
+        n_tiles = sum(int(w["lm"][1]) * int(w["lm"][2]) for w in sc.walls)
+        tiles = np.random.default_rng(5).integers(0, 256, 3 * n_tiles, dtype=np.uint8)
+        c = fmgi.camera(pixel=span / W, **cam)
+        rows = {0.0: [], G: []}
+        stats = {}
+        for r in range(2 + a.rounds):
+            for g in ((0.0, G) if r % 2 == 0 else (G, 0.0)):
+                fmgi.shade_views(sc, c, W, H, tiles, (7, 8, 9), samples=S, filter=a.filter, gloss=g)
+                st = fmgi.view_stats()
+                stats[g] = (st, fmgi.view_gloss_stats())
+                if r >= 2:
+                    rows[g].append(st["rays_ms"])
+        (st0, _), (st1, gs) = stats[0.0], stats[G]
+        t0, t1 = min(rows[0.0]), min(rows[G])
+        per_test[name] = t0 * 1e6 / max(st0["tests"], 1)
+        res = {"metric": "k_view_shade_gloss against k_view_shade", "case": name, "walls": int(len(sc.walls)), "width": W,
+               "height": H, "samples": S, "filter": a.filter, "gloss": G, "rounds": a.rounds, "n_gpus": 1,
+               "kernel_ms": {"gloss_0": spread(rows[0.0]), "gloss": spread(rows[G])}, "rays": st1["rays"],
+               "primary_tests": st0["tests"], "mirror_rays": gs["mirror_rays"], "mirror_hits": gs["mirror_hits"],
+               "mirror_tests": gs["mirror_tests"], "tests_per_ray": st0["tests"] / st0["rays"],
+               "tests_per_mirror_ray": gs["mirror_tests"] / max(gs["mirror_rays"], 1),
+               "mirror_share": gs["mirror_rays"] / st1["rays"], "all_samples_mirror": gs["mirror_rays"] == st1["rays"],
+               "ns_per_test_gloss_0": per_test[name], "time_ratio": t1 / t0,
+               "ns_per_mirror_test": (t1 - t0) * 1e6 / max(gs["mirror_tests"], 1)}
+        if name == "box200_floor":
+            res["yardstick_ns_per_test_box2000"] = per_test["box2000"]
+            res["ratio_to_yardstick"] = res["ns_per_mirror_test"] / per_test["box2000"]
+            res["within_1.10"] = bool(res["ratio_to_yardstick"] <= 1.10)
+        # the traced view: the trace with and without mirror records, shade per picture with and without gloss
+        dev = f"cuda:{int(os.environ.get('FMGI_DEVICE', 0))}"
+        tiles_dev = torch.from_numpy(tiles).to(dev)
+        rgb_dev = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        trace = {}
+        for mirror in (False, True):
+            ms = []
+            for _ in range(3):
+                vc = fmgi.ViewCache(sc, c, W, H, S, a.filter, mirror=mirror)
+                ms.append(vc.info()["trace_ms"])
+                if len(ms) < 3:
+                    vc.close()
+            trace["mirror" if mirror else "plain"] = min(ms)
+            if not mirror:
+                vc.close()
+        shade = {}
+        for g in (0.0, G):
+            ms = []
+            for r in range(2 + a.rounds):
+                ev[0].record()
+                vc.shade([tiles_dev.data_ptr()], [rgb_dev.data_ptr()], (7, 8, 9), gloss=g)
+                ev[1].record()
+                ev[1].synchronize()
+                if r >= 2:
+                    ms.append(ev[0].elapsed_time(ev[1]))
+            shade["gloss_0" if g == 0 else "gloss"] = min(ms)
+        host = fmgi.shade_views(sc, c, W, H, tiles, (7, 8, 9), samples=S, filter=a.filter, gloss=G)["rgb"][0]
+        res["traced_view"] = {"trace_ms": trace, "bytes": vc.info()["bytes"], "shade_ms": shade,
+                              "equal_to_shade_views": bool(np.array_equal(rgb_dev.cpu().numpy(), host))}
+        vc.close()
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--projection", choices=("ortho", "equirect"), default=None,
                     help="time this camera's k_view_shade_proj against the pin-hole k_view_shade instead")
+    ap.add_argument("--gloss", type=float, default=None,
+                    help="time the glossy floor at this mirror weight (0 < G <= 1) against the matt floor instead")
     ap.add_argument("--samples", type=int, default=4, help="--projection: N x N rays per pixel")
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear", help="--projection: the tile filter")
     ap.add_argument("--rounds", type=int, default=7, help="--projection: timed rounds after two warm-up rounds")
@@ -121,6 +211,10 @@ def main():
     ap.add_argument("--height", type=int, default=3072)
     ap.add_argument("--no-shade", action="store_true", help="fmgi_render_views only")
     a = ap.parse_args()
+    if a.gloss is not None:
+        if a.projection or not 0 < a.gloss <= 1:
+            ap.error("--gloss takes a weight in (0, 1] and the pin-hole camera")
+        return gloss_main(a)
     if a.projection:
         return projection_main(a)
     import fmgi

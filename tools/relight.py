@@ -8,6 +8,7 @@ once into one histogram per group of sources: all windows together, and the ligh
 place of photonmap.cl's constants would give. Each result is finalised, normalised and turned into the walls'
 RGB8 tiles (fmgi.output_tiles), and written to OUT/<name>/texels.npy (float32 [numTexels, 4], normalised) and
 OUT/<name>/tiles.npy (uint8). With --view a camera picture (fmgi.shade_views) goes to OUT/<name>/view.ppm.
+--gloss G draws that picture's floor with one mirror bounce.
 
 The scenario file is a JSON list; every entry has a name and a palette per group:
 
@@ -112,6 +113,17 @@ def scenario_palettes(entry, groups):
     return row
 
 
+def gloss_value(text):
+    """--gloss: a number in [0, 1]"""
+    try:
+        g = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not 0.0 <= g <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text} is outside [0, 1]")
+    return g
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
@@ -136,6 +148,9 @@ def parse_args(argv=None):
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
     ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
                     help="--view's camera model: pin-hole, orthographic plan (--pixel metres per pixel), or panorama")
+    ap.add_argument("--gloss", type=gloss_value, default=0.0,
+                    help="--view: the floor's mirror weight in [0, 1], one mirror bounce from every floor sample "
+                         "(default 0: matt)")
     ap.add_argument("--min-deposits", type=int, default=0,
                     help="adaptive density filter: grow every texel's window until it holds the energy of N "
                          "first-bounce window photons (default 0: no filter)")
@@ -289,7 +304,7 @@ def main(argv=None):
         # the camera's rays are cast once; every scenario's picture is gathered from its device texels
         vdev = f"cuda:{int(os.environ.get('FMGI_DEVICE', 0))}"  # the device of the geometry-based calls
         vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter,
-                            projection=a.projection)
+                            projection=a.projection, mirror=a.gloss > 0)
         nbytes = max(3 * vc.info()["tiles"], 1)
         vs = torch.cuda.Stream(device=vdev)
         with torch.cuda.stream(vs):
@@ -299,7 +314,7 @@ def main(argv=None):
                 rgb_dev = [torch.empty((a.height, a.width, 3), dtype=torch.uint8, device=vdev) for _ in part]
                 vc.tiles([t.data_ptr() for t in part], a.spa, [t.data_ptr() for t in tiles_dev], stream=vs.cuda_stream)
                 vc.shade([t.data_ptr() for t in tiles_dev], [t.data_ptr() for t in rgb_dev], tuple(a.background),
-                         stream=vs.cuda_stream)
+                         stream=vs.cuda_stream, gloss=a.gloss)
                 views += rgb_dev
         vs.synchronize()
         views = [v.cpu().numpy() for v in views]

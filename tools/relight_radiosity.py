@@ -14,7 +14,7 @@ windows, (28, 28, 32) for lights), finite and >= 0.
 
 Writes OUT/<name>/texels.npy (float32 [numTexels, 4]) and tiles.npy (the RGB8 tiles of the reference's radiosity
 mode: numSamplesPerArea = 0, tintExtra = 1) and, with --view, view.ppm: one ViewCache casts the camera's rays once
-and shades every scenario from the device texels the solve left.
+and shades every scenario from the device texels the solve left; --gloss G draws the floor with one mirror bounce.
 """
 import argparse
 import json
@@ -76,6 +76,17 @@ def scenario_emit(entries, num_windows, num_lights):
     return names, np.stack(emit).astype(np.float32).reshape(len(names), num_windows + num_lights, 3)
 
 
+def gloss_value(text):
+    """--gloss: a number in [0, 1]"""
+    try:
+        g = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not 0.0 <= g <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text} is outside [0, 1]")
+    return g
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
@@ -96,6 +107,9 @@ def parse_args(argv=None):
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="bilinear")
     ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
                     help="--view's camera model: pin-hole, orthographic plan (--pixel metres per pixel), or panorama")
+    ap.add_argument("--gloss", type=gloss_value, default=0.0,
+                    help="--view: the floor's mirror weight in [0, 1], one mirror bounce from every floor sample "
+                         "(default 0: matt)")
     return ap.parse_args(argv)
 
 
@@ -121,7 +135,7 @@ def main(argv=None):
         texels = rc.solve(emit, a.iterations, stream=st)
         if a.view:
             vc = fmgi.ViewCache(sc, fmgi.camera(a.pos, a.dir, a.up, a.pixel), a.width, a.height, a.samples, a.filter,
-                                projection=a.projection)
+                                projection=a.projection, mirror=a.gloss > 0)
             nbytes = max(3 * vc.info()["tiles"], 1)
             for k0 in range(0, len(names), fmgi.VIEW_CACHE_MAX_SETS):
                 part = [texels[k] for k in range(k0, min(k0 + fmgi.VIEW_CACHE_MAX_SETS, len(names)))]
@@ -129,7 +143,7 @@ def main(argv=None):
                 rgb_dev = [torch.empty((a.height, a.width, 3), dtype=torch.uint8, device=dev) for _ in part]
                 vc.tiles([t.data_ptr() for t in part], SPA, [t.data_ptr() for t in tiles_dev], TINT, stream=st.cuda_stream)
                 vc.shade([t.data_ptr() for t in tiles_dev], [t.data_ptr() for t in rgb_dev], tuple(a.background),
-                         stream=st.cuda_stream)
+                         stream=st.cuda_stream, gloss=a.gloss)
                 views += rgb_dev
     st.synchronize()
     if a.view:

@@ -21,6 +21,12 @@ picture has --width = 2 * --height); both go through fmgi.shade_views:
   python tools/render_view.py flat.bin --texels out/texels.npy --spa 172413793 --projection ortho --pos 6 5 10 \\
       --dir 0 0 -1 --up 0 1 0 --pixel 0.01 --width 1400 --height 1100 --samples 4 --filter bilinear -o plan.ppm
 
+--gloss G (0..1) draws the floor as the bake treats it: a sample that lands on the floor casts one mirror ray and
+takes G of its colour from what that ray sees (fmgi.shade_views(gloss=G)); 0 is the matt floor:
+
+  python tools/render_view.py flat.bin --texels out/texels.npy --spa 172413793 --samples 4 --filter bilinear \\
+      --gloss 0.75 -o glossy.ppm
+
 A PNG is written next to the PPM when PIL can be imported.
 """
 import argparse
@@ -58,6 +64,17 @@ def write_ppm(path, rgb):
         f.write(np.ascontiguousarray(rgb, np.uint8).tobytes())
 
 
+def gloss_value(text):
+    """--gloss: a number in [0, 1]"""
+    try:
+        g = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not 0.0 <= g <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text} is outside [0, 1]")
+    return g
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", help="geometry fixture path, or box8 / box200 / box2000")
@@ -76,6 +93,8 @@ def main(argv=None):
     ap.add_argument("--filter", choices=("nearest", "bilinear"), default="nearest", help="how a ray reads the tiles")
     ap.add_argument("--projection", choices=("pinhole", "ortho", "equirect"), default="pinhole",
                     help="camera model: pin-hole, orthographic plan, or equirectangular panorama")
+    ap.add_argument("--gloss", type=gloss_value, default=0.0,
+                    help="the floor's mirror weight in [0, 1]: one mirror bounce from every floor sample (default 0: matt)")
     ap.add_argument("-o", "--output", default="view.ppm")
     a = ap.parse_args(argv)
     import fmgi
@@ -89,17 +108,21 @@ def main(argv=None):
     else:
         tiles = wall_colour_tiles(sc)
     cam = fmgi.camera(a.pos, a.dir, a.up, a.pixel)
-    if a.samples == 1 and a.filter == "nearest" and a.projection == "pinhole":
+    if a.samples == 1 and a.filter == "nearest" and a.projection == "pinhole" and a.gloss == 0:
         out = fmgi.render_views(sc, cam, a.width, a.height, tiles_rgb=tiles, background=tuple(a.background))
         hits, unit = int((out["wall"] >= 0).sum()), "pixels"
     else:
         out = fmgi.shade_views(sc, cam, a.width, a.height, tiles, tuple(a.background), samples=a.samples, filter=a.filter,
-                               projection=a.projection)
+                               projection=a.projection, gloss=a.gloss)
         hits, unit = int(out["coverage"].sum(dtype=np.int64)), "rays"
     write_ppm(a.output, out["rgb"][0])
     st = fmgi.view_stats()
     print(f"{a.output}: {a.width}x{a.height}, {hits} of {st['rays']} {unit} hit a wall, "
           f"{st['candidates']} candidates, {st['tests'] / max(st['rays'], 1):.1f} tests/ray, {st['total_ms']:.2f} ms")
+    if a.gloss:
+        gs = fmgi.view_gloss_stats()
+        print(f"  gloss {a.gloss:g}: {gs['mirror_rays']} mirror rays, {gs['mirror_hits']} hit a wall, "
+              f"{gs['mirror_tests'] / max(gs['mirror_rays'], 1):.1f} tests/mirror ray")
     try:
         from PIL import Image
     except ImportError:
