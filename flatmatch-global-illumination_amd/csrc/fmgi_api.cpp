@@ -32,6 +32,7 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_internal.h"
+#include "fmgi_sun.h"
 #include "fmgi_filter.h"
 #include "fmgi_recolour.h"
 #include "fmgi_sparse.h"
@@ -955,6 +956,9 @@ struct fmgi_context {
     size_t hist_bytes = 0;
     unsigned long long *d_hist_lm = nullptr;
     unsigned long long *d_hist_stats = nullptr;
+    /* the direct-sun layer (fmgi_sun_host.cpp): host copies of the walls and windows, and its device
+       tables and scratch; made by the first fmgi_set_scene */
+    SunState *sun = nullptr;
 };
 
 /* releases the held sparse histogram and the scratch lightmap of fmgi_bake_sparse (hipFree waits for the device) */
@@ -969,6 +973,14 @@ static void hist_release(fmgi_context *c) {
 
 /* the closed-box (one plane per axis and class) instances off: FMGI_OPT_NO_AXES (tests; at fmgi_set_scene) */
 static bool no_axes(const fmgi_context *c) { return c->opt[FMGI_OPT_NO_AXES] != 0 || fmgi_exp_env("FMGI_NO_AXES"); }
+
+/* the sun layer's view of a context (fmgi_sun.h) */
+bool fmgi_sun_ctx(fmgi_context *c, SunCtx *out) {
+    if (!c) return false;
+    if (!c->sun) c->sun = fmgi_sun_new(); /* no scene yet: the calls report FMGI_ERR_STATE */
+    *out = SunCtx{c->sun, c->device, c->num_cus, c->num_texels, c->stream};
+    return true;
+}
 
 FMGI_API const char *fmgi_version(void) { return "fmgi 0.1 (gfx950)"; }
 FMGI_API const char *fmgi_last_error(void) { return g_err.c_str(); }
@@ -1021,10 +1033,12 @@ FMGI_API fmgi_context *fmgi_create(int device) {
 FMGI_API void fmgi_destroy(fmgi_context *c) {
     if (!c) return;
     if (c->device == FMGI_HOST_ONLY) {
+        fmgi_sun_free(c->sun, false);
         delete c;
         return;
     }
     hipSetDevice(c->device);
+    fmgi_sun_free(c->sun, true);
     if (c->stream) hipStreamSynchronize(c->stream);
     hipFree(c->d_rects);
     hipFree(c->d_srcs);
@@ -1517,6 +1531,8 @@ FMGI_API int fmgi_set_scene(fmgi_context *c, const fmgi_rect *walls, int num_wal
             return set_err(FMGI_ERR_ARG, "wall %d: lightmapSetup {%d,%d,%d} outside %d texels", i, lm[0], lm[1],
                            lm[2], num_texels);
     }
+    if (!c->sun) c->sun = fmgi_sun_new();
+    fmgi_sun_set_scene(c->sun, walls, num_walls, windows, num_windows);
     std::vector<RectDev> rd((size_t)num_walls);
     for (int i = 0; i < num_walls; i++) rd[i] = make_rect(walls[i]);
     std::vector<SrcDev> sd;

@@ -26,6 +26,7 @@ from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM,
                    VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewGlossStats, ViewStats, check,
                    PROJ_EQUIRECT, PROJ_ORTHO, PROJ_PINHOLE,
                    RAD_CACHE_MAX_ITERATIONS, RAD_CACHE_MAX_SETS, RadCacheInfo,
+                   SUN_ALL, SUN_LISTS, SUN_MAX_MAPS, SUN_MAX_SAMPLES, SunStats,
                    load)
 from .scene import RECT_DTYPE, Scene
 
@@ -92,6 +93,11 @@ __all__ = [
     "scene_hash",
     "save_bake",
     "load_bake",
+    "sun_vector",
+    "SUN_LISTS",
+    "SUN_ALL",
+    "SUN_MAX_SAMPLES",
+    "SUN_MAX_MAPS",
 ]
 
 
@@ -118,6 +124,17 @@ def host_sincosf(x):
     c = np.empty_like(x)
     load().fmgi_host_sincosf(_ptr(x), _ptr(s), _ptr(c), len(x))
     return s, c
+
+
+def sun_vector(azimuth_deg: float, elevation_deg: float) -> np.ndarray:
+    """The to_sun vector of a compass azimuth (degrees clockwise from north, +y is north, +x east) and an elevation
+    above the horizon (degrees): float32 (sin az * cos el, cos az * cos el, sin el). The sun calls normalise it, so
+    its float32 rounding only moves the direction by an ulp."""
+    az, el = np.radians(float(azimuth_deg)), np.radians(float(elevation_deg))
+    return np.array([np.sin(az) * np.cos(el), np.cos(az) * np.cos(el), np.sin(el)], np.float32)
+
+
+_SUN_MODES = {"lists": SUN_LISTS, "all": SUN_ALL}
 
 
 def palette_table(p: Palette) -> np.ndarray:
@@ -477,6 +494,48 @@ class Context:
         op = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p) or None) for p in out_ptrs])
         check(self.lib.fmgi_filter_apply(self.h, C.c_void_p(radii_ptr or None), ip, op, K, C.c_void_p(stream or None)),
               "fmgi_filter_apply")
+
+    def sun_coverage(self, to_sun, samples: int, cover_ptr: int, mode: str = "lists", stream: int = 0):
+        """fmgi_sun_coverage: per level-0 texel of every wall that faces the sun, how many of its
+        samples x samples shadow rays towards to_sun (any non-zero length) leave through a window before they meet a
+        wall, into the device array uint8 [num_texels] at cover_ptr; every other byte 0. mode "lists" (per-window
+        occluder lists, the product path) or "all" (every wall that faces away from the sun): the same bytes.
+        Asynchronous on `stream`."""
+        if mode not in _SUN_MODES:
+            raise FmgiError(f"mode {mode!r}: one of {sorted(_SUN_MODES)}")
+        v = (C.c_float * 3)(*[float(x) for x in to_sun])
+        check(self.lib.fmgi_sun_coverage(self.h, v, int(samples), _SUN_MODES[mode], C.c_void_p(cover_ptr or None),
+                                         C.c_void_p(stream or None)), "fmgi_sun_coverage")
+
+    def sun_add(self, cover_ptr: int, to_sun, samples: int, rgb, flux: float, lm_ptrs, stream: int = 0):
+        """fmgi_sun_add: adds the sun of colour rgb[k] (palette units; window_rgb is 18) and `flux` photons per m²
+        (the bake's spa) through the coverage map at cover_ptr (made with the same to_sun and samples) to the device
+        lightmap int64 [num_texels][4] at lm_ptrs[k], in place. rgb is [K][3], or one colour for one map.
+        Asynchronous on `stream`."""
+        rgb = np.ascontiguousarray(np.atleast_2d(np.asarray(rgb, np.float32)))
+        K = len(lm_ptrs)
+        if rgb.shape != (K, 3):
+            raise FmgiError(f"sun_add: {K} lightmaps, rgb of shape {rgb.shape}")
+        v = (C.c_float * 3)(*[float(x) for x in to_sun])
+        lp = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p) or None) for p in lm_ptrs])
+        check(self.lib.fmgi_sun_add(self.h, C.c_void_p(cover_ptr or None), v, int(samples), _ptr(rgb), K, float(flux),
+                                    lp, C.c_void_p(stream or None)), "fmgi_sun_add")
+
+    def sun_stats(self) -> dict:
+        """fmgi_sun_get_stats of the context's last sun_coverage (synchronises): samples, facing, crossing, lit,
+        list_entries, tests, list_ms, rays_ms."""
+        st = SunStats()
+        check(self.lib.fmgi_sun_get_stats(self.h, C.byref(st)), "fmgi_sun_get_stats")
+        return st.as_dict()
+
+    def sun_units(self, to_sun, rgb, flux: float) -> np.ndarray:
+        """fmgi_sun_units (host only): int64 [numWalls][3], what one fully lit texel of every wall gains in units of
+        2^-25; zero rows for the walls that do not face the sun."""
+        v = (C.c_float * 3)(*[float(x) for x in to_sun])
+        c = (C.c_float * 3)(*[float(x) for x in rgb])
+        out = np.zeros((len(self.scene.walls) if self.scene is not None else 0, 3), np.int64)
+        check(self.lib.fmgi_sun_units(self.h, v, c, float(flux), out.ctypes.data_as(C.c_void_p)), "fmgi_sun_units")
+        return out
 
     def source_ranges(self):
         """One (source, is_window, item_begin, item_end) per emitter of the planned schedule, windows first: the

@@ -113,6 +113,10 @@ EXPORTS = (
     "fmgi_filter_energy",
     "fmgi_filter_radii",
     "fmgi_filter_apply",
+    "fmgi_sun_coverage",
+    "fmgi_sun_get_stats",
+    "fmgi_sun_add",
+    "fmgi_sun_units",
 )
 
 KERNEL_EXACT = 0
@@ -139,6 +143,10 @@ RECOLOUR_MAX_SCENARIOS = 8
 SPARSE_COUNT_BITS = 54
 FILTER_MAX_RADIUS = 16
 FILTER_MAX_MAPS = 8
+SUN_MAX_SAMPLES = 8
+SUN_MAX_MAPS = 8
+SUN_LISTS = 0
+SUN_ALL = 1
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
            "no_axes": 7, "photon_lock": 8, "lattice": 9, "hist_batch": 10}
@@ -164,6 +172,24 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SunStats(C.Structure):
+    """fmgi_sun_stats (include/flatmatch_gi.h)."""
+
+    _fields_ = [
+        ("samples", C.c_int64),
+        ("facing", C.c_int64),
+        ("crossing", C.c_int64),
+        ("lit", C.c_int64),
+        ("list_entries", C.c_int64),
+        ("tests", C.c_int64),
+        ("list_ms", C.c_double),
+        ("rays_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: (float if k.endswith("ms") else int)(getattr(self, k)) for k, _ in self._fields_}
 
 
 class Timing(C.Structure):
@@ -486,6 +512,10 @@ def load() -> C.CDLL:
         "fmgi_filter_energy": (u64, [C.POINTER(Palette), u64]),
         "fmgi_filter_radii": (C.c_int, [vp, vp, u64, C.c_int, vp, vp]),
         "fmgi_filter_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
+        "fmgi_sun_coverage": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+        "fmgi_sun_get_stats": (C.c_int, [vp, C.POINTER(SunStats)]),
+        "fmgi_sun_add": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, vp, vp]),
+        "fmgi_sun_units": (C.c_int, [vp, vp, vp, C.c_double, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_lattice_copy": (C.c_int, [vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),

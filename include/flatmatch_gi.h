@@ -651,6 +651,72 @@ int fmgi_filter_radii(fmgi_context *ctx, const void *guide_lm_fx_dev, uint64_t m
 int fmgi_filter_apply(fmgi_context *ctx, const void *radii_dev, const void *const *lm_in_dev,
                       void *const *lm_out_dev, int num_maps, void *stream);
 
+/* ---- Direct sunlight through windows: a relightable lightmap layer ------------------ */
+/* The bake treats a window as a diffuse patch of sky. The sun is a direction: its light on a flat rectangle is
+   colour x cosine x the fraction of each texel that sees the sun through a window, and that fraction is a count of
+   sub-texel shadow rays. It needs no photons, has no noise and does not depend on the bake: one coverage map per
+   sun direction serves every colour and scenario, and fmgi_sun_add drops it into the int64 lightmap that
+   fmgi_recolour, fmgi_filter_apply, fmgi_finalize and the traced views pass around. No reference counterpart; the
+   semantics below are the interface.
+
+   All arithmetic is IEEE fp32 without contraction, in the order written. dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+   intersects(r, src, dir, closest) is rectangle.c:67-95 (the hit distance, or -1), on a rectangle's unit edges and
+   lengths precomputed with the operations the AO, radiosity and view paths use (width * (1 / |width|), |v| =
+   sqrtf((x*x + y*y) + z*z)).
+     Sun vector   to_sun[3] points from the scene to the sun, any non-zero finite length:
+                  l = sqrtf((x*x + y*y) + z*z), s = (x/l, y/l, z/l).
+     Facing       c_w = dot(n_w, s); wall w receives sun only if c_w > 0.
+     Samples      the level-0 texel (tx, ty) of wall w (lightmapSetup = {s0, s1, s2, 0}, index s0 + ty*s1 + tx) has
+                  S x S samples (i, j): a = ((float)tx + (float)(2i+1) / (float)(2S)) / (float)s1, b likewise from
+                  ty, j, s2; P = (pos + width*a) + height*b per component; Q = P + s*1e-5f.
+     Crossing     d_v = intersects(window v, Q, s, +INFINITY), the window as the scene holds it: its normal points
+                  into the room and the ray towards the sun runs against it, which is the side intersects' first
+                  line lets through. dw = the smallest d_v that is not -1; a sample with no crossing is not lit.
+                  Lights are not windows.
+     Occlusion    the sample is blocked if any wall i of the scene gives intersects(wall_i, Q, s, dw) != -1. Any-hit:
+                  the result depends neither on the order nor on which walls are skipped, as long as a skipped wall
+                  could not have hit. A wall behind the window's plane fails intersects' own distance test.
+     Coverage     cover[t], a uint8, is the number of lit samples of texel t, 0..S*S; 0 for every texel in no facing
+                  wall's level-0 grid (the mip levels too). The call writes all numTexels bytes.
+     Energy       the sun is `flux` photons per m^2 perpendicular to s, each carrying rgb in the palette's units
+                  (window_rgb is 18); flux is the bake's numSamplesPerArea. For a facing wall, in doubles, multiplied
+                  left to right: unit[w][c] = (int64)floor(ldexp((double)rgb[c] * (double)c_w * flux * area_t, 25)),
+                  area_t = ((double)|width| * (double)|height|) / (double)(s1*s2) with the fp32 lengths above.
+                  lm_fx[t][c] += (cover[t] * unit[w][c] + S*S/2) / (S*S) in integers; lm_fx[t][3] is not touched.
+                  After fmgi_finalize and main.c:68-79's normalisation with the same numSamplesPerArea a fully lit
+                  texel gains 0.35 * rgb[c] * c_w.
+   Out of scope: the sun's bounced light, a penumbra, sun entering other than through a window rectangle.
+
+   All calls use the scene of fmgi_set_scene (walls and windows). fmgi_sun_coverage and fmgi_sun_add are
+   asynchronous on `stream`; to_sun and rgb are read before the call returns. FMGI_SUN_ALL tests every wall with
+   dot(n_i, s) < 0 (the others return -1 by intersects' first line); FMGI_SUN_LISTS, the product path, tests per
+   window only the walls of a conservative occluder list and gives the same bytes and the same four
+   counts. Arguments are checked on the host before any device call, in this order: FMGI_ERR_ARG for a NULL context
+   or pointer, samples outside 1..FMGI_SUN_MAX_SAMPLES, a mode that is neither of the two, a to_sun of zero or
+   non-finite length, num_maps < 1, an rgb component that is not finite or outside [0, 32), a flux that is not
+   finite or <= 0; FMGI_ERR_STATE without a scene; FMGI_ERR_ARG if a unit reaches 2^55 (its product with a count
+   of at most 64 then stays below 2^62); FMGI_ERR_NO_DEVICE on a host-only context. A scene without windows and a
+   direction no wall faces give an all-zero map and success. The calls' tables, lists and counters live in scratch
+   memory of the context; a later call's stream waits for the earlier call, the host does not. */
+#define FMGI_SUN_MAX_SAMPLES 8
+#define FMGI_SUN_MAX_MAPS 8            /* maps one pass of fmgi_sun_add carries; the call takes any number */
+enum { FMGI_SUN_LISTS = 0, FMGI_SUN_ALL = 1 };
+struct fmgi_sun_stats {                 /* of the context's last fmgi_sun_coverage; get synchronises */
+    int64_t samples, facing, crossing, lit;   /* samples of all level-0 texels, of the facing walls' texels, those that
+                                                 cross a window, those that are lit; order-independent */
+    int64_t list_entries, tests;              /* informational: occluder-list lengths summed, intersects() run */
+    double list_ms, rays_ms;                  /* device time of the list kernel and of the ray kernel */
+};
+int fmgi_sun_coverage(fmgi_context *ctx, const float to_sun[3], int samples, int mode,
+                      void *cover_dev /* uint8 [numTexels] */, void *stream);
+int fmgi_sun_get_stats(fmgi_context *ctx, struct fmgi_sun_stats *out);
+/* lm_fx_dev[k] += the deposits of cover_dev (made with the same to_sun and samples) under rgb[k], in place */
+int fmgi_sun_add(fmgi_context *ctx, const void *cover_dev, const float to_sun[3], int samples,
+                 const float *rgb /* [num_maps][3] */, int num_maps, double flux,
+                 void *const *lm_fx_dev, void *stream);
+/* host only, works on FMGI_HOST_ONLY contexts: units[numWalls][3], zero rows for walls that do not face */
+int fmgi_sun_units(fmgi_context *ctx, const float to_sun[3], const float rgb[3], double flux, int64_t *units);
+
 /* The kernel FMGI_KERNEL_AUTO resolves to for the current scene. */
 int fmgi_auto_kernel(const fmgi_context *ctx);
 /* The profiler's name of the k_bake instance the last bake launch ran ("void (anonymous namespace)::k_bake<...>

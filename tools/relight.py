@@ -21,6 +21,12 @@ A palette may set window_rgb, light_rgb, floor_tint, albedo (defaults: the refer
 every light group, or with --per-light a list with one palette per light. A histogram takes 8 KiB per texel and
 group of device memory.
 
+An entry may also carry a sun: "sun": {"azimuth": 200, "elevation": 35, "rgb": [30, 28, 24]} (degrees; +y is north,
+fmgi.sun_vector) or "sun": {"to_sun": [x, y, z], "rgb": [..]}. Its direct light through the windows is
+added to that scenario's lightmap after the filter and before it is finalised: --sun-samples N x N shadow rays per
+texel, one coverage map per distinct direction of the file, the flux the bake's --spa. It needs no photons and is
+the same on the dense, --sparse and --load-bake routes.
+
 A bake of few photons is speckled; --min-deposits N smooths every scenario's lightmap with the adaptive density
 filter before it is finalised: per texel a window of radius <= --max-radius, grown until it
 holds the energy of N first-bounce window photons in the reference-palette lightmap of all groups, so all
@@ -113,6 +119,49 @@ def scenario_palettes(entry, groups):
     return row
 
 
+def sun_of(entry):
+    """A scenario entry's sun: None without a "sun" key, else (to_sun float32 [3], rgb [r, g, b]). The object holds
+    "rgb" and either "azimuth" and "elevation" in degrees (fmgi.sun_vector: +y is north) or "to_sun": [x, y, z]."""
+    import fmgi
+
+    if "sun" not in entry:
+        return None
+    where = f"scenario {entry.get('name')!r}: sun"
+    spec = entry["sun"]
+    if not isinstance(spec, dict):
+        raise SystemExit(f"{where} must be an object with rgb and azimuth + elevation, or rgb and to_sun")
+    unknown = set(spec) - {"azimuth", "elevation", "to_sun", "rgb"}
+    if unknown:
+        raise SystemExit(f"{where} keys {sorted(unknown)}: azimuth, elevation, to_sun or rgb")
+
+    def numbers(value, n, what):
+        ok = (isinstance(value, (list, tuple)) and len(value) == n
+              and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in value))
+        if not ok or not np.all(np.isfinite(np.asarray(value, np.float64))):
+            raise SystemExit(f"{where}: {what} must be {n} finite number{'s' if n > 1 else ''}")
+        return [float(v) for v in value]
+
+    if "rgb" not in spec:
+        raise SystemExit(f"{where} needs rgb: [r, g, b] in the palette's units (window_rgb is 18)")
+    rgb = numbers(spec["rgb"], 3, "rgb")
+    if not all(0.0 <= v < 32.0 for v in rgb):
+        raise SystemExit(f"{where}: rgb must lie in [0, 32)")
+    if "to_sun" in spec:
+        if "azimuth" in spec or "elevation" in spec:
+            raise SystemExit(f"{where} takes to_sun or azimuth + elevation, not both")
+        to_sun = np.array(numbers(spec["to_sun"], 3, "to_sun"), np.float32)
+    elif "azimuth" in spec and "elevation" in spec:
+        az, = numbers([spec["azimuth"]], 1, "azimuth")
+        el, = numbers([spec["elevation"]], 1, "elevation")
+        to_sun = fmgi.sun_vector(az, el)
+    else:
+        raise SystemExit(f"{where} needs azimuth and elevation, or to_sun")
+    length = float(np.sqrt(np.sum(to_sun.astype(np.float64) ** 2)))
+    if not np.isfinite(length) or not length > 0:
+        raise SystemExit(f"{where}: the direction has no length")
+    return to_sun, rgb
+
+
 def gloss_value(text):
     """--gloss: a number in [0, 1]"""
     try:
@@ -155,6 +204,8 @@ def parse_args(argv=None):
                     help="adaptive density filter: grow every texel's window until it holds the energy of N "
                          "first-bounce window photons (default 0: no filter)")
     ap.add_argument("--max-radius", type=int, default=4, help="the filter's largest window radius in texels (0..16)")
+    ap.add_argument("--sun-samples", type=int, default=4,
+                    help="scenarios with a sun: N x N shadow rays per texel (1..8, default 4)")
     ap.add_argument("--sparse", action="store_true",
                     help="compact every group's histogram into its sparse form and recolour from the blobs")
     ap.add_argument("--save-bake", default=None, metavar="FILE", help="write the traced scene to FILE (implies --sparse)")
@@ -177,6 +228,8 @@ def parse_args(argv=None):
         ap.error("--min-deposits must not be negative")
     if not 0 <= a.max_radius <= 16:
         ap.error("--max-radius must be in 0..16")
+    if not 1 <= a.sun_samples <= 8:
+        ap.error("--sun-samples must be in 1..8")
     return a
 
 
@@ -193,6 +246,7 @@ def main(argv=None):
     names = [str(e["name"]) for e in entries]
     if len(set(names)) != len(names) or any(os.sep in n or n in ("", ".", "..") for n in names):
         sys.exit(f"{a.scenarios}: scenario names must be distinct directory names")
+    suns = [sun_of(e) for e in entries]  # a malformed one ends the run here
     sc = load_scene(a.scene, a.tile_size, a.with_light)
     loaded = None
     if a.load_bake is not None:  # every mismatch ends the run here, before a device context exists
@@ -272,6 +326,18 @@ def main(argv=None):
                              s.cuda_stream)
             ptrs = [lm.data_ptr() for lm in lms]
             ctx.filter_apply(radii.data_ptr(), ptrs, ptrs, s.cuda_stream)
+        # direct sun, after the filter: it is not noise and must not be smoothed. One coverage map per
+        # distinct direction of the file; every scenario of that direction adds its colour through it
+        by_dir = {}
+        for k, sun in enumerate(suns):
+            if sun is not None:
+                by_dir.setdefault(sun[0].tobytes(), []).append(k)
+        for ks in by_dir.values():
+            to_sun = suns[ks[0]][0]
+            cover = torch.empty(max(T, 1), dtype=torch.uint8, device=dev)
+            ctx.sun_coverage(to_sun, a.sun_samples, cover.data_ptr(), stream=s.cuda_stream)
+            ctx.sun_add(cover.data_ptr(), to_sun, a.sun_samples, [suns[k][1] for k in ks], a.spa,
+                        [lms[k].data_ptr() for k in ks], s.cuda_stream)
         zero = torch.zeros((T, 4), dtype=torch.float32, device=dev)
         texels = [torch.empty((T, 4), dtype=torch.float32, device=dev) for _ in entries]
         for lm, t in zip(lms, texels):
@@ -296,6 +362,9 @@ def main(argv=None):
                   f"histogram: {fmgi.states_bytes(T) / 2**20:.1f} MiB), {sum(v[0] for v in from_codes)} dense chunks")
         if a.save_bake is not None:
             print(f"  bake saved to {a.save_bake}: {os.path.getsize(a.save_bake)} bytes")
+    if by_dir:
+        print(f"  sun: {len(by_dir)} direction{'s' if len(by_dir) > 1 else ''}, {a.sun_samples} x {a.sun_samples} "
+              f"rays per texel, {sum(len(ks) for ks in by_dir.values())} scenarios")
     if a.min_deposits > 0:
         print(f"  filtered: {a.min_deposits} deposits, radius <= {a.max_radius}, mean radius "
               f"{radii.float().mean().item():.3f}")
