@@ -111,8 +111,33 @@ struct HitRec {
     float bux, buy, buz, bvx, bvy, bvz;
 };
 
-/* photonmap.cl:123-158 (closest = INFINITY) on rect r (index idx), filling h's rect fields and dx, dy */
-template <class R>
+/* intersect_exact_uv (fmgi_core.h) with no return before the end, for the trimmed loop of k_bake_locked: the same
+   operations in the same order, and the four rejections joined into the one select of -1. A whole wave of a closed
+   box practically never leaves early, so the two early returns (denom >= 0, fac < 0) only cost their mask
+   round trips and branches. A lane that would have returned early divides by a non-negative or zero denom (no trap
+   is enabled) and is selected away; a NaN passes every comparison, as it does there; every other lane gets the
+   same bits in fac, dx and dy. A rejected lane's dx, dy are not read (the fallback rewrites the HitRec). */
+__device__ __forceinline__ float intersect_exact_uv_flat(f3 n, f3 pos, f3 wn, float wl, f3 hn, float hl, f3 src,
+                                                         f3 dir, float &dx, float &dy) {
+    const float denom = dot3(n, dir);
+    const float fac = dot3(n, sub3(pos, src)) / denom;
+    const f3 pDir = sub3(add3(src, mul3(dir, fac)), pos);
+    dx = dot3(wn, pDir);
+    dy = dot3(hn, pDir);
+    const bool out = (int)(denom >= 0) | (int)(fac < 0) | (int)(dx < 0) | (int)(dx > wl) | (int)(dy < 0) | (int)(dy > hl);
+    return out ? -1.0f : fac;
+}
+
+template <bool Flat>
+__device__ __forceinline__ float exact_uv(f3 n, f3 pos, f3 wn, float wl, f3 hn, float hl, f3 src, f3 dir, float &dx,
+                                          float &dy) {
+    if constexpr (Flat) return intersect_exact_uv_flat(n, pos, wn, wl, hn, hl, src, dir, dx, dy);
+    else return intersect_exact_uv(n, pos, wn, wl, hn, hl, src, dir, dx, dy);
+}
+
+/* photonmap.cl:123-158 (closest = INFINITY) on rect r (index idx), filling h's rect fields and dx, dy
+   (Flat: through intersect_exact_uv_flat) */
+template <bool Flat = false, class R>
 __device__ __forceinline__ float exact_hit_rec(const R &r, int idx, f3 src, f3 dir, HitRec &h) {
     h.idx = idx;
     h.nx = r.nx; h.ny = r.ny; h.nz = r.nz;
@@ -121,21 +146,21 @@ __device__ __forceinline__ float exact_hit_rec(const R &r, int idx, f3 src, f3 d
     h.base = r.base; h.W = r.W; h.H = r.H;
     h.bux = r.bux; h.buy = r.buy; h.buz = r.buz;
     h.bvx = r.bvx; h.bvy = r.bvy; h.bvz = r.bvz;
-    return intersect_exact_uv(mkf3(r.nx, r.ny, r.nz), mkf3(r.px, r.py, r.pz), mkf3(r.wnx, r.wny, r.wnz), r.wl,
-                              mkf3(r.hnx, r.hny, r.hnz), r.hl, src, dir, h.dx, h.dy);
+    return exact_uv<Flat>(mkf3(r.nx, r.ny, r.nz), mkf3(r.px, r.py, r.pz), mkf3(r.wnx, r.wny, r.wnz), r.wl,
+                          mkf3(r.hnx, r.hny, r.hnz), r.hl, src, dir, h.dx, h.dy);
 }
 
 /* the same on rect idx, read from the workgroup's LDS copy of the table (RectLds records) when the host
    staged it there (BakeArgs::rects_off >= 0), else from global memory; the two reads stay in their own address
    spaces (a pointer that may be either compiles to flat loads, which wait on both counters) */
-template <bool Staged = false>
+template <bool Staged = false, bool Flat = false>
 __device__ __forceinline__ float exact_hit(const BakeArgs &a, const char *lds, int idx, f3 src, f3 dir, HitRec &h) {
     if (Staged || uni(a.rects_off) >= 0)
-        return exact_hit_rec(*(const __attribute__((address_space(3))) RectLds *)(
-                                 (const __attribute__((address_space(3))) char *)lds + a.rects_off +
-                                 __umul24((uint32_t)idx, (uint32_t)sizeof(RectLds))), /* not the quarter-rate v_mul_lo_u32 */
-                             idx, src, dir, h);
-    return exact_hit_rec(((gptr<RectDev>)a.rects)[idx], idx, src, dir, h);
+        return exact_hit_rec<Flat>(*(const __attribute__((address_space(3))) RectLds *)(
+                                       (const __attribute__((address_space(3))) char *)lds + a.rects_off +
+                                       __umul24((uint32_t)idx, (uint32_t)sizeof(RectLds))), /* not the quarter-rate v_mul_lo_u32 */
+                                   idx, src, dir, h);
+    return exact_hit_rec<Flat>(((gptr<RectDev>)a.rects)[idx], idx, src, dir, h);
 }
 
 /* the global table (rare paths: fallbacks, ScanExact) */
@@ -146,6 +171,7 @@ __device__ __forceinline__ float exact_hit(const BakeArgs &a, int idx, f3 src, f
 /* phase 2 on the compact closed-box tables (fmgi_internal.h RectC / ClassC, staged in LDS): the same
    intersect_exact_uv on the same bit patterns as exact_hit_rec's RectLds / RectDev fields; 1 / length is
    v_rcp_f32 (tile_uv's quotient estimate needs only one ulp) */
+template <bool Flat = false>
 __device__ __forceinline__ float exact_hit_compact(const BakeArgs &a, const char *lds, int idx, f3 src, f3 dir,
                                                    HitRec &h) {
     typedef const __attribute__((address_space(3))) char *lp;
@@ -165,8 +191,8 @@ __device__ __forceinline__ float exact_hit_compact(const BakeArgs &a, const char
     h.W = (int)(wh & 0xFFFFu); h.H = (int)(wh >> 16);
     h.bux = k.bux; h.buy = k.buy; h.buz = k.buz;
     h.bvx = k.bvx; h.bvy = k.bvy; h.bvz = k.bvz;
-    return intersect_exact_uv(mkf3(h.nx, h.ny, h.nz), mkf3(px, py, pz), mkf3(k.wnx, k.wny, k.wnz), wl,
-                              mkf3(k.hnx, k.hny, k.hnz), hl, src, dir, h.dx, h.dy);
+    return exact_uv<Flat>(mkf3(h.nx, h.ny, h.nz), mkf3(px, py, pz), mkf3(k.wnx, k.wny, k.wnz), wl,
+                          mkf3(k.hnx, k.hny, k.hnz), hl, src, dir, h.dx, h.dy);
 }
 
 /* the result of a literal scan (hit, best) as a HitRec (rare paths: ScanExact, fallbacks) */
@@ -814,7 +840,7 @@ __device__ __forceinline__ void grid_nearest_cell(const BakeArgs &a, const char 
  * the lattice sees one, so `ties` and `invalid` may fall and `tests` does; hits, deposits and RNG draws do not
  * change.
  */
-template <bool Staged, bool Compact = false, bool Lattice = false>
+template <bool Staged, bool Compact = false, bool Lattice = false, bool Guard = false>
 __device__ __forceinline__ void grid_phase1_axes(const BakeArgs &a, const char *img, f3 s, f3 d, float &L1,
                                                  float &L2, int &code1, unsigned &ntest) {
     const float fx0 = (*(const float *)(img + (d.x < 0.0f ? 0 : 64)) - s.x) * __builtin_amdgcn_rcpf(d.x);
@@ -858,6 +884,11 @@ __device__ __forceinline__ void grid_phase1_axes(const BakeArgs &a, const char *
         }
     }
     const int m = mz ? 2 : (my ? 1 : 0); /* the others, within the band above the current L1 (1 + 2^-11) */
+    /* Guard (the trimmed loop of k_bake_locked): one test in front of the three. fx, fy, fz hold no NaN and fm is
+       their minimum, so their median f2 is the smaller fac' of the two other planes; L1 is fm or INFINITY here.
+       f2 above the band means both others are (no visit, L1 unchanged: what the three tests find, one by one);
+       f2 inside it runs them as they are. box200 visits a far plane on 0.1 % of its points. */
+    if (Guard && !(__builtin_amdgcn_fmed3f(fx, fy, fz) <= L1 * 1.00048828125f)) return;
     if (m != 0 && fx < INFINITY && fx <= L1 * 1.00048828125f) grid_axes_visit<0, Staged, Compact>(a, img, s, d, fx, L1, L2, code1, ntest);
     if (m != 1 && fy < INFINITY && fy <= L1 * 1.00048828125f) grid_axes_visit<1, Staged, Compact>(a, img, s, d, fy, L1, L2, code1, ntest);
     if (m != 2 && fz < INFINITY && fz <= L1 * 1.00048828125f) grid_axes_visit<2, Staged, Compact>(a, img, s, d, fz, L1, L2, code1, ntest);
@@ -959,6 +990,9 @@ struct ScanGridImpl {
         return -2; /* more candidates than rounds: caller runs the full literal scan */
     }
 
+    /* Trim: the caller is the trimmed loop of k_bake_locked (the AccShared instances, measured for them alone:
+       profiles/step_trim): phase 1's far-plane guard and phase 2's exact test without early returns */
+    template <bool Trim = false>
     static __device__ __forceinline__ void scan(const BakeArgs &a, const char *lds, f3 src, f3 dir, HitRec &h,
                                                 ScanStats &st) {
         float L1 = INFINITY, L2 = INFINITY;
@@ -968,7 +1002,7 @@ struct ScanGridImpl {
         int code1 = -1;
         unsigned ntest = 0;
         if (Axes) {
-            grid_phase1_axes<Staged, Compact, Lattice>(a, lds, src, dir, L1, L2, code1, ntest);
+            grid_phase1_axes<Staged, Compact, Lattice, Trim>(a, lds, src, dir, L1, L2, code1, ntest);
         } else if (a.fJ[0] + a.fJ[1] + a.fJ[2] <= 4) {
             grid_phase1_sorted(a, lds, src, dir, L1, L2, code1, ntest);
         } else {
@@ -1007,7 +1041,8 @@ struct ScanGridImpl {
             return;
         }
         const int idx = code1; /* rect index of the phase-1 winner */
-        const float f = Compact ? exact_hit_compact(a, lds, idx, src, dir, h) : exact_hit<Staged>(a, lds, idx, src, dir, h);
+        const float f = Compact ? exact_hit_compact<Trim>(a, lds, idx, src, dir, h)
+                                : exact_hit<Staged, Trim>(a, lds, idx, src, dir, h);
         const bool sep = !(f < 0) && L2 > f * 1.000244140625f; /* ScanFast's separation test */
         st.clk.lap(ST_SCAN2);
         if (sep) {
@@ -1990,7 +2025,9 @@ struct AccScatter {
  *     one opener at a time), refilled with one pool-cursor atomic for up to kBatch blocks (fewer while the
  *     tile has filled few blocks, so a tile that gets little leaves little unused). One reserve per
  *     workgroup, refilled by whichever opener found it empty, lost a batch whenever two tiles' openers
- *     refilled at once, which was the rule, and ran the pool dry (profiles/shared_buckets/README.md).
+ *     refilled at once, which was the rule, and ran the pool dry (profiles/shared_buckets/README.md). In the
+ *     trimmed loop of k_bake_locked the opener also refills a reserve it has emptied after it has moved the word
+ *     on (refill, append<true>), so the next opener rarely waits for the pool.
  *   - Ranks past 2 BP hold no slot: they are the first F - 2 BP positions of block seq + 2 in the new numbering
  *     (F: the fill the opener's add returned). No lane will ever get rank == BP of seq + 1 then, so the same
  *     lane goes on as that seq's opener: it stores sentinels (which the fold skips) in those slots and repeats
@@ -2062,7 +2099,28 @@ struct AccShared {
         return (uint32_t)first;
     }
 
-    /* the opener of (t, seq), see above: one lane, rarely */
+    /* tile t's reserve refilled where it has run dry, by the opener that has just moved the tile's word on: the pool
+       atomic's round trip is then behind the block switch, not inside it, where every code of rank >= 2 BP that
+       arrives meanwhile takes the fallback (a workgroup fills a block of a one-tile lightmap in under two
+       iterations). The tile can have its next opener before this store lands: that one finds the reserve empty
+       and refills it itself (take), and one of the two batches stays in no reserve. Every block of a batch is
+       recorded empty here, and the stores are complete before the reserve shows them, so such blocks are what an
+       unused reserve's blocks are at the end of the launch; no block is in two batches (one pool atomic each). */
+    static __device__ __forceinline__ void refill(const BakeArgs &a, u64 *V, uint32_t t, uint32_t seq) {
+        const u64 v = ld(V);
+        if ((uint32_t)v < (uint32_t)(v >> 32)) return;
+        const uint32_t want = seq / 4u + 1u < kBatch ? seq / 4u + 1u : kBatch;
+        const u64 first = atomicAdd(a.pool_cursor, (u64)want);
+        if (first >= a.pool_blocks) return;
+        const u64 hi = first + want < a.pool_blocks ? first + want : a.pool_blocks;
+#pragma nounroll
+        for (uint32_t b = (uint32_t)first; b < (uint32_t)hi; b++) a.block_tile[b] = t, a.block_len[b] = 0u;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __hip_atomic_store(V, (hi << 32) | first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+
+    /* the opener of (t, seq), see above: one lane, rarely (Ahead: with refill, below append) */
+    template <bool Ahead>
     static __device__ __forceinline__ void open(const BakeArgs &a, u64 *W, u64 *R, u64 *V, uint32_t t, uint32_t seq) {
         uint32_t holes = 0; /* leading slots of block seq + 1 whose positions took the fallback */
         for (int step = 0;; step++, seq++) {
@@ -2087,7 +2145,10 @@ struct AccShared {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             const uint32_t F = (uint32_t)__hip_atomic_fetch_add(W + t, (1ull << 32) - BP, __ATOMIC_RELAXED,
                                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (F <= 2 * BP) return;
+            if (F <= 2 * BP) {
+                if (Ahead) refill(a, V + t, t, seq + 1); /* (for the next opener: off the path the lanes wait on) */
+                return;
+            }
             holes = F - 2 * BP;
         }
     }
@@ -2099,6 +2160,9 @@ struct AccShared {
         AccBucket::bucket_atomic(a, code);
     }
 
+    /* Ahead (the trimmed loop of k_bake_locked, whose shorter iteration leaves an opener less time): the opener
+       refills its tile's reserve after the block switch (refill); the other loops keep the code they had */
+    template <bool Ahead = false>
     static __device__ __forceinline__ void append(const BakeArgs &a, WaveStream &, uint32_t *base, bool dep,
                                                   uint32_t code) {
         if (!dep) return;
@@ -2118,7 +2182,7 @@ struct AccShared {
             fallback(a, code, rank < 2 * BP && tag != want);
         }
         /* (the opener's own code, slot 0 of block seq + 1, is stored by now: its registers are free) */
-        if (rank == BP) open(a, W, R, reserve(base), t, seq);
+        if (rank == BP) open<Ahead>(a, W, R, reserve(base), t, seq);
     }
 
     /* after the loop, once every wave of the workgroup has stored its codes: one lane per tile records the
@@ -2739,7 +2803,9 @@ __device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
  *    its photons short of FMGI_MAX_DEPTH each, where a photon escapes; the wave's scans are FMGI_MAX_DEPTH a
  *    photon less these (32 bits: a lane traces a few dozen items per launch);
  *  - AccShared::append is a lane's own business (LaneAppend) and is called where the lane deposits, so neither
- *    the code nor `dep` is a value joined over the escape and the parked lanes.
+ *    the code nor `dep` is a value joined over the escape and the parked lanes;
+ *  - the scan is Scan::scan<true> (profiles/step_trim): phase 1's three far-plane band tests behind one guard on
+ *    the median of the planes' distances, phase 2's exact test without early returns (intersect_exact_uv_flat).
  * The two empty asm statements only steer the compiler; whether they still do is read off the listing.
  */
 template <class Scan, class Acc, bool TRACE>
@@ -2859,7 +2925,7 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
 
                     /* ---- stage 2: scan ---- */
                     HitRec h;
-                    Scan::scan(a, s_img, pos, dir, h, sst);
+                    Scan::template scan<kTrim>(a, s_img, pos, dir, h, sst);
                     sst.clk.lap(ST_SCAN1);
                     sn = mkf3(h.nx, h.ny, h.nz);
                     sbu = mkf3(h.bux, h.buy, h.buz);
@@ -2941,7 +3007,7 @@ __global__ __launch_bounds__(1024) FMGI_BAKE_ATTR void k_bake_locked(BakeArgs a)
                             ((EventDev *)a.events)[(item - a.item_begin) * FMGI_EVENTS_PER_ITEM + nev] = e;
                             nev++;
                         }
-                        if constexpr (kTrim) Acc::append(a, ws, ring, true, code);
+                        if constexpr (kTrim) Acc::template append<true>(a, ws, ring, true, code);
                     }
                     sst.clk.lap(ST_HIT);
                 }

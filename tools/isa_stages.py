@@ -42,6 +42,8 @@ STAGE_OF_FUNC = [
     ("exact_on_v", "fallback (rare)"),
     ("intersect_exact", "fallback (rare)"),
     ("intersect_exact_uv", "phase 2: exact intersects()"),
+    ("intersect_exact_uv_flat", "phase 2: exact intersects()"),
+    ("exact_uv", "phase 2: exact intersects()"),
     ("exact_hit_rec", "phase 2: record fields"),
     ("exact_hit_compact", "phase 2: record fields"),
     ("exact_hit", "phase 2: record fields"),
