@@ -13,7 +13,8 @@
  *   - runs the device phases (fmgi_rad.hip) and copies texels [0, numTexels) back;
  *   - leaves the libc generator exactly where 2 x 10000 x jobs rand() calls would have left it.
  * fmgi_rad_cache_*  runs the same trace once (rad_prepare, rad_trace), keeps its ids on the device and
- * solves any emitter palettes from them, asynchronously on the caller's stream.
+ * solves any emitter palettes from them, asynchronously on the caller's stream; fmgi_rad_cache_sun_bounce
+ * gathers sun coverage maps through the same ids (fmgi_sun_bounce.hip).
  * Geometry precomputation is fp32 in the reference's order (built with -ffp-contract=off, no FMA).
  */
 #include <hip/hip_runtime_api.h>
@@ -28,6 +29,7 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_rad.h"
+#include "fmgi_sun_bounce.h"
 #include "fmgi_view.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
@@ -632,6 +634,22 @@ done:
     return rc;
 }
 
+/* the scratch tables with room for kp_need slots of 16 B per texel; the caller has waited for what used them */
+int rad_tables(fmgi_rad_cache *c, int kp_need) {
+    int rc = FMGI_OK;
+    if (c->table_kp < kp_need) {
+        const size_t tb = (size_t)c->ntex * (size_t)kp_need * 16;
+        c->table_kp = 0;
+        c->src.release(), c->dst.release(), c->dest.release();
+        RADCHK(c->src.alloc(tb));
+        RADCHK(c->dst.alloc(tb));
+        RADCHK(c->dest.alloc(tb));
+        c->table_kp = kp_need;
+    }
+done:
+    return rc;
+}
+
 int rad_cache_solve(fmgi_rad_cache *c, const float *emit, int num_sets, int iterations, void *const *texels_dev,
                     hipStream_t st) {
     static const char fn[] = "fmgi_rad_cache_solve";
@@ -657,15 +675,7 @@ int rad_cache_solve(fmgi_rad_cache *c, const float *emit, int num_sets, int iter
     if (c->table_kp < kp_need || c->params_cap < bytes) { /* grow the scratch once nothing uses it any more */
         if (c->pending) RADCHK(hipEventSynchronize(c->ev_solve));
         c->pending = false;
-        if (c->table_kp < kp_need) {
-            const size_t tb = (size_t)c->ntex * (size_t)kp_need * 16;
-            c->table_kp = 0;
-            c->src.release(), c->dst.release(), c->dest.release();
-            RADCHK(c->src.alloc(tb));
-            RADCHK(c->dst.alloc(tb));
-            RADCHK(c->dest.alloc(tb));
-            c->table_kp = kp_need;
-        }
+        if ((rc = rad_tables(c, kp_need)) != FMGI_OK) goto done;
         if (c->params_cap < bytes) {
             c->params_cap = 0;
             c->params.release();
@@ -721,6 +731,91 @@ done:
     return rc;
 }
 
+
+static_assert(FMGI_SUN_BOUNCE_DIRS == FMGI_SUN_BOUNCE_MAX_DIRS && FMGI_SUN_BOUNCES == FMGI_SUN_MAX_BOUNCES,
+              "kernel and ABI limits differ");
+
+/* DESIGN §21. The per-direction values go to the kernels as arguments: nothing of the caller's is read later. */
+int rad_cache_sun_bounce(fmgi_rad_cache *c, void *const *cover_dev, const float *to_sun, const int *samples, int num_dirs,
+                         int bounces, void *const *bounce_dev, hipStream_t st) {
+    static const char fn[] = "fmgi_rad_cache_sun_bounce";
+    if (!c || !cover_dev || !to_sun || !samples || !bounce_dev) return arg_err(fn, "null argument");
+    if (num_dirs < 1) return arg_err(fn, "num_dirs < 1");
+    if (bounces < 1 || bounces > FMGI_SUN_MAX_BOUNCES) return arg_err(fn, "bounces outside 1..8");
+    std::vector<float> s((size_t)num_dirs * 3);
+    for (int k = 0; k < num_dirs; k++) {
+        if ((!cover_dev[k] || !bounce_dev[k]) && c->num_texels) return arg_err(fn, "a coverage map or an output is NULL");
+        if (samples[k] < 1 || samples[k] > FMGI_SUN_MAX_SAMPLES) return arg_err(fn, "samples outside 1..8");
+        if (!fmgi_sun_unit_vector(to_sun + 3 * (size_t)k, &s[3 * (size_t)k]))
+            return arg_err(fn, "to_sun has a zero or non-finite length");
+    }
+    {
+        int dev_count = 0;
+        if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1)
+            return internal_set_err(FMGI_ERR_NO_DEVICE, "no HIP device visible");
+    }
+    if (c->num_texels == 0) return FMGI_OK; /* no walls: nothing to gather and nothing to write */
+
+    int rc = FMGI_OK;
+    const int first_pass = std::min(num_dirs, FMGI_SUN_BOUNCE_MAX_DIRS);
+    int kp_first = 1;
+    while (kp_first < first_pass) kp_first <<= 1;
+    const int kp_need = std::max(1, kp_first / 4); /* the scratch counts slots of 16 B */
+    SunBounce b;
+    memset(&b, 0, sizeof b);
+    RADCHK(hipSetDevice(c->device));
+    if (c->table_kp < kp_need) { /* grow the scratch once nothing uses it any more */
+        if (c->pending) RADCHK(hipEventSynchronize(c->ev_solve));
+        c->pending = false;
+        if ((rc = rad_tables(c, kp_need)) != FMGI_OK) goto done;
+    }
+    /* an earlier call, maybe on another stream, may still use the scratch */
+    if (c->pending) RADCHK(hipStreamWaitEvent(st, c->ev_solve, 0));
+    b.sids = c->sids.as<int32_t>();
+    b.jobs = c->jobs.as<RadJob>();
+    b.njobs = c->njobs;
+    b.rects = c->rects.as<RadRect>();
+    b.nwalls = c->first_emit;
+    b.ntex = c->ntex;
+    b.num_texels = c->num_texels;
+    for (int k0 = 0; k0 < num_dirs; k0 += FMGI_SUN_BOUNCE_MAX_DIRS) {
+        const int n = std::min(FMGI_SUN_BOUNCE_MAX_DIRS, num_dirs - k0);
+        float *src = c->src.as<float>(), *dst = c->dst.as<float>();
+        SunBounceDirs d;
+        memset(&d, 0, sizeof d);
+        for (int k = 0; k < n; k++) {
+            d.cover[k] = (const uint8_t *)cover_dev[k0 + k];
+            d.out[k] = (float *)bounce_dev[k0 + k];
+            d.sx[k] = s[3 * (size_t)(k0 + k)], d.sy[k] = s[3 * (size_t)(k0 + k) + 1], d.sz[k] = s[3 * (size_t)(k0 + k) + 2];
+            d.s2[k] = (float)(samples[k0 + k] * samples[k0 + k]);
+        }
+        b.kp = 1;
+        while (b.kp < n) b.kp <<= 1;
+        b.ndirs = n;
+        const size_t tb = (size_t)c->ntex * (size_t)b.kp * 4;
+        /* both tables start at +0: the padding slots, the texels no wall faces and no ray starts from. Every later
+           round overwrites exactly the jobs' texels, which are the level-0 texels the start table fills. */
+        RADCHK(hipMemsetAsync(src, 0, tb, st));
+        RADCHK(hipMemsetAsync(dst, 0, tb, st));
+        b.src = nullptr;
+        b.dst = src;
+        RADCHK(fmgi_sun_bounce_launch_e0(b, d, st));
+        for (int it = 0; it < bounces; it++) {
+            b.src = src;
+            b.dst = dst;
+            RADCHK(fmgi_sun_bounce_launch_gather(b, st));
+            b.src = dst;
+            b.row = it;
+            RADCHK(fmgi_sun_bounce_launch_unpack(b, d, st));
+            std::swap(src, dst);
+        }
+    }
+    RADCHK(hipEventRecord(c->ev_solve, st));
+    c->pending = true;
+done:
+    return rc;
+}
+
 } // namespace
 
 FMGI_API int64_t fmgi_rad_cache_bytes(const fmgi_geometry *geo) {
@@ -764,6 +859,13 @@ FMGI_API int fmgi_rad_reference_emit(const fmgi_geometry *geo, float *emit) {
 FMGI_API int fmgi_rad_cache_solve(const fmgi_rad_cache *c, const float *emit, int num_sets, int iterations,
                                   void *const *texels_dev, void *stream) {
     return rad_cache_solve(const_cast<fmgi_rad_cache *>(c), emit, num_sets, iterations, texels_dev, (hipStream_t)stream);
+}
+
+FMGI_API int fmgi_rad_cache_sun_bounce(const fmgi_rad_cache *c, void *const *cover_dev, const float *to_sun,
+                                       const int *samples, int num_dirs, int bounces, void *const *bounce_dev,
+                                       void *stream) {
+    return rad_cache_sun_bounce(const_cast<fmgi_rad_cache *>(c), cover_dev, to_sun, samples, num_dirs, bounces, bounce_dev,
+                                (hipStream_t)stream);
 }
 
 FMGI_API int fmgi_radiosity(const fmgi_geometry *geo, fmgi_vec3 *texels_out, int32_t *sids_out) {

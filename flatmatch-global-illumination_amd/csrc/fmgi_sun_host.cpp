@@ -1,7 +1,8 @@
 /*
  * fmgi_sun_host.cpp -- host side of the direct-sun layer and its C ABI (include/flatmatch_gi.h: fmgi_sun_coverage,
- * fmgi_sun_get_stats, fmgi_sun_add, fmgi_sun_units). No reference program has a sun: the header states
- * the semantics, tests/sun_restate.py restates them.
+ * fmgi_sun_get_stats, fmgi_sun_add, fmgi_sun_units) and of the bounced layer's add (fmgi_sun_add_bounced,
+ * DESIGN §21). No reference program has a sun: the header states the semantics, tests/sun_restate.py and
+ * tests/sun_bounce_restate.py restate them.
  *
  * The context keeps host copies of the scene's walls and windows (fmgi_sun_set_scene) and, on a device context, their
  * intersects() records, the occluder lists, a call's job table and unit table and the counters. A call checks its
@@ -21,13 +22,15 @@
 
 #include "../../include/flatmatch_gi.h"
 #include "fmgi_sun.h"
+#include "fmgi_sun_bounce.h"
 #include "fmgi_view.h"
 
 #define FMGI_API extern "C" __attribute__((visibility("default")))
 
 int internal_set_err(int code, const char *msg);
 
-static_assert(FMGI_SUN_SAMPLES == FMGI_SUN_MAX_SAMPLES && FMGI_SUN_MAPS == FMGI_SUN_MAX_MAPS,
+static_assert(FMGI_SUN_SAMPLES == FMGI_SUN_MAX_SAMPLES && FMGI_SUN_MAPS == FMGI_SUN_MAX_MAPS &&
+                  FMGI_SUN_BOUNCE_MAPS == FMGI_SUN_MAX_MAPS && FMGI_SUN_BOUNCES == FMGI_SUN_MAX_BOUNCES,
               "kernel and ABI limits differ");
 
 /* a pinned block a call builds its tables in; free again once `done` has completed */
@@ -52,6 +55,8 @@ struct SunState {
     size_t jobs_cap = 0;
     long long *d_units = nullptr;
     size_t units_cap = 0;
+    SunBounceWall *d_bounce_walls = nullptr; /* fmgi_sun_add_bounced's wall table */
+    size_t bounce_walls_cap = 0;
     hipEvent_t ev = nullptr; /* after the last launch of the context's last sun call */
     bool pending = false;
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr}; /* around the last coverage call's two kernels */
@@ -232,6 +237,7 @@ void fmgi_sun_free(SunState *st, bool has_device) {
         hipFree(st->d_counters);
         hipFree(st->d_jobs);
         hipFree(st->d_units);
+        hipFree(st->d_bounce_walls);
     }
     delete st;
 }
@@ -427,6 +433,84 @@ FMGI_API int fmgi_sun_add(fmgi_context *ctx, const void *cover_dev, const float 
         a.num_texels = c.num_texels;
         for (int m = 0; m < a.maps; m++) a.lm[m] = (unsigned long long *)lm_fx_dev[k0 + m];
         e = fmgi_sun_launch_add(a, q);
+    }
+    const hipError_t ev = hipEventRecord(st.ev, q);
+    if (e != hipSuccess) return err(FMGI_ERR_HIP, fn, hipGetErrorString(e));
+    SUNCHK(ev);
+    return FMGI_OK;
+}
+
+/* the bounce tables of one direction under num_maps colours and reflectances, onto every wall */
+FMGI_API int fmgi_sun_add_bounced(fmgi_context *ctx, const void *bounce_dev, int bounces, const float *rgb,
+                                  const float *refl, int num_maps, double flux, void *const *lm_fx_dev, void *stream) {
+    static const char fn[] = "fmgi_sun_add_bounced";
+    SunCtx c;
+    if (!fmgi_sun_ctx(ctx, &c) || !bounce_dev || !rgb || !refl || !lm_fx_dev) return err(FMGI_ERR_ARG, fn, "null argument");
+    if (bounces < 1 || bounces > FMGI_SUN_MAX_BOUNCES) return err(FMGI_ERR_ARG, fn, "bounces outside 1..8");
+    if (num_maps < 1) return err(FMGI_ERR_ARG, fn, "num_maps < 1");
+    for (int k = 0; k < num_maps; k++)
+        if (!lm_fx_dev[k]) return err(FMGI_ERR_ARG, fn, "a lightmap is NULL");
+    if (bad_rgb(rgb, num_maps)) return err(FMGI_ERR_ARG, fn, "an rgb component is not finite or outside [0, 32)");
+    for (int k = 0; k < 3 * num_maps; k++)
+        if (!isfinite(refl[k]) || !(refl[k] >= 0.0f && refl[k] <= 1.0f))
+            return err(FMGI_ERR_ARG, fn, "a refl component is not finite or outside [0, 1]");
+    if (!isfinite(flux) || !(flux > 0)) return err(FMGI_ERR_ARG, fn, "flux is not finite and positive");
+    SunState &st = *c.sun;
+    if (!st.scene_set) return err(FMGI_ERR_STATE, fn, "no scene");
+    const size_t nw = st.walls.size();
+    std::vector<SunBounceWall> walls(nw);
+    int64_t total = 0;
+    double max_area = 0;
+    for (size_t i = 0; i < nw; i++) {
+        const AoRect &r = st.hits[i];
+        const int32_t *lm = st.walls[i].lightmapSetup;
+        SunBounceWall &w = walls[i];
+        memset(&w, 0, sizeof w);
+        w.s0 = lm[0];
+        w.n = lm[1] * lm[2];
+        w.first = (int32_t)total;
+        w.area_t = ((double)r.wl * (double)r.hl) / (double)((int64_t)lm[1] * lm[2]);
+        max_area = std::max(max_area, w.area_t);
+        total += w.n; /* fmgi_set_scene: s0 + s1 * s2 <= numTexels, an int */
+    }
+    /* g_n <= 1 up to rounding, a reflectance's powers <= 1, rgb < 32: no deposit reaches 2^55 */
+    if (!(ldexp(32.0 * (double)bounces * 1.001 * flux * max_area, 25) < 36028797018963968.0))
+        return err(FMGI_ERR_ARG, fn, "a deposit may reach 2^55: flux * texel area is too large");
+    if (c.device == FMGI_HOST_ONLY) return err(FMGI_ERR_NO_DEVICE, fn, "host-only context");
+
+    SUNCHK(hipSetDevice(c.device));
+    hipStream_t q = stream ? (hipStream_t)stream : c.stream;
+    if (nw == 0 || total == 0) return FMGI_OK;
+    int rc = device_tables(st);
+    if (rc != FMGI_OK) return rc;
+    if ((rc = grow(&st.d_bounce_walls, &st.bounce_walls_cap, nw)) != FMGI_OK) return rc;
+    SunStage *stage = nullptr;
+    if ((rc = stage_acquire(st, nw * sizeof(SunBounceWall), &stage)) != FMGI_OK) return rc;
+    memcpy(stage->host, walls.data(), nw * sizeof(SunBounceWall));
+    if (st.pending) SUNCHK(hipStreamWaitEvent(q, st.ev, 0));
+    st.pending = true;
+    hipError_t e = hipMemcpyAsync(st.d_bounce_walls, stage->host, nw * sizeof(SunBounceWall), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipEventRecord(stage->done, q);
+    stage->pending = true;
+    for (int k0 = 0; k0 < num_maps && e == hipSuccess; k0 += FMGI_SUN_BOUNCE_MAPS) {
+        SunBounceAdd a;
+        memset(&a, 0, sizeof a);
+        a.walls = st.d_bounce_walls;
+        a.nwalls = (int)nw;
+        a.total = (int)total;
+        a.bounce = (const float *)bounce_dev;
+        a.bounces = bounces;
+        a.maps = std::min(FMGI_SUN_BOUNCE_MAPS, num_maps - k0);
+        a.num_texels = c.num_texels;
+        a.flux = flux;
+        for (int m = 0; m < a.maps; m++) {
+            for (int ch = 0; ch < 3; ch++) {
+                a.rgb[m][ch] = rgb[3 * (size_t)(k0 + m) + ch];
+                a.refl[m][ch] = refl[3 * (size_t)(k0 + m) + ch];
+            }
+            a.lm[m] = (unsigned long long *)lm_fx_dev[k0 + m];
+        }
+        e = fmgi_sun_bounce_launch_add(a, q);
     }
     const hipError_t ev = hipEventRecord(st.ev, q);
     if (e != hipSuccess) return err(FMGI_ERR_HIP, fn, hipGetErrorString(e));

@@ -26,7 +26,7 @@ from ._lib import (ACCUM_AUTO, ACCUM_FX3, ACCUM_NONE, ACCUM_STATE, ACCUM_STREAM,
                    VIEW_BILINEAR, VIEW_CACHE_MAX_SETS, VIEW_MAX_SAMPLES, VIEW_NEAREST, ViewCacheInfo, ViewGlossStats, ViewStats, check,
                    PROJ_EQUIRECT, PROJ_ORTHO, PROJ_PINHOLE,
                    RAD_CACHE_MAX_ITERATIONS, RAD_CACHE_MAX_SETS, RadCacheInfo,
-                   SUN_ALL, SUN_LISTS, SUN_MAX_MAPS, SUN_MAX_SAMPLES, SunStats,
+                   SUN_ALL, SUN_BOUNCE_MAX_DIRS, SUN_LISTS, SUN_MAX_BOUNCES, SUN_MAX_MAPS, SUN_MAX_SAMPLES, SunStats,
                    load)
 from .scene import RECT_DTYPE, Scene
 
@@ -98,6 +98,8 @@ __all__ = [
     "SUN_ALL",
     "SUN_MAX_SAMPLES",
     "SUN_MAX_MAPS",
+    "SUN_BOUNCE_MAX_DIRS",
+    "SUN_MAX_BOUNCES",
 ]
 
 
@@ -521,6 +523,21 @@ class Context:
         check(self.lib.fmgi_sun_add(self.h, C.c_void_p(cover_ptr or None), v, int(samples), _ptr(rgb), K, float(flux),
                                     lp, C.c_void_p(stream or None)), "fmgi_sun_add")
 
+    def sun_add_bounced(self, bounce_ptr: int, bounces: int, rgb, refl, flux: float, lm_ptrs, stream: int = 0):
+        """fmgi_sun_add_bounced: adds the sun's bounced light, the device table float32
+        [bounces][num_texels] of one direction at bounce_ptr (RadCache.sun_bounce), under colour rgb[k] and
+        reflectance refl[k] per channel to the device lightmap int64 [num_texels][4] at lm_ptrs[k], in place: bounce n
+        weighs refl ** n. rgb and refl are [K][3], or one triple for one map; flux is the bake's spa.
+        Asynchronous on `stream`."""
+        rgb = np.ascontiguousarray(np.atleast_2d(np.asarray(rgb, np.float32)))
+        refl = np.ascontiguousarray(np.atleast_2d(np.asarray(refl, np.float32)))
+        K = len(lm_ptrs)
+        if rgb.shape != (K, 3) or refl.shape != (K, 3):
+            raise FmgiError(f"sun_add_bounced: {K} lightmaps, rgb of shape {rgb.shape}, refl of shape {refl.shape}")
+        lp = (C.c_void_p * max(K, 1))(*[C.c_void_p(int(p) or None) for p in lm_ptrs])
+        check(self.lib.fmgi_sun_add_bounced(self.h, C.c_void_p(bounce_ptr or None), int(bounces), _ptr(rgb), _ptr(refl), K,
+                                            float(flux), lp, C.c_void_p(stream or None)), "fmgi_sun_add_bounced")
+
     def sun_stats(self) -> dict:
         """fmgi_sun_get_stats of the context's last sun_coverage (synchronises): samples, facing, crossing, lit,
         list_entries, tests, list_ms, rays_ms."""
@@ -887,6 +904,41 @@ class RadCache:
         ptrs, n = _ptr_array(out[i].data_ptr() for i in range(k))
         check(self.lib.fmgi_rad_cache_solve(self.h, emit.ctypes.data_as(C.c_void_p), n, iterations, ptrs,
                                             C.c_void_p(handle or None)), "fmgi_rad_cache_solve")
+        return out
+
+
+    def sun_bounce(self, covers, to_suns, samples, bounces: int, stream=None):
+        """fmgi_rad_cache_sun_bounce: covers are K coverage maps on the device (torch uint8 tensors of
+        num_texels bytes, or addresses; Context.sun_coverage), to_suns float32 [K, 3] their directions, samples their
+        samples per texel edge (one int for all, or K) -> a torch float32 device tensor [K, bounces, num_texels]: row
+        n - 1 is g_n, the n-th bounce of a sun of unit colour on walls of unit reflectance. Asynchronous on `stream`:
+        a torch.cuda.Stream, a hipStream_t integer, or None for torch's current stream."""
+        import os
+
+        import torch
+
+        covers = list(covers)
+        k = len(covers)
+        to_suns = np.ascontiguousarray(np.asarray(to_suns, np.float32).reshape(-1, 3))
+        samples = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, np.int32), (k,)))
+        if to_suns.shape != (k, 3):
+            raise FmgiError(f"sun_bounce: {k} coverage maps, to_suns of shape {to_suns.shape}")
+        for c in covers:
+            if hasattr(c, "data_ptr") and (c.dtype != torch.uint8 or c.numel() < self.num_texels or not c.is_contiguous()):
+                raise FmgiError(f"sun_bounce: a coverage map is uint8 [{self.num_texels}], contiguous")
+        dev = torch.device("cuda", int(os.environ.get("FMGI_DEVICE", "0")))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        out = torch.empty((k, int(bounces), self.num_texels), dtype=torch.float32, device=dev)
+        if isinstance(stream, int):
+            handle = stream
+        else:
+            handle = stream.cuda_stream
+            out.record_stream(stream)
+        cp, _ = _ptr_array(c.data_ptr() if hasattr(c, "data_ptr") else c for c in covers)
+        op, _ = _ptr_array(out[i].data_ptr() for i in range(k))
+        check(self.lib.fmgi_rad_cache_sun_bounce(self.h, cp, _ptr(to_suns), _ptr(samples), k, int(bounces), op,
+                                                 C.c_void_p(handle or None)), "fmgi_rad_cache_sun_bounce")
         return out
 
 

@@ -117,6 +117,8 @@ EXPORTS = (
     "fmgi_sun_get_stats",
     "fmgi_sun_add",
     "fmgi_sun_units",
+    "fmgi_rad_cache_sun_bounce",
+    "fmgi_sun_add_bounced",
 )
 
 KERNEL_EXACT = 0
@@ -147,6 +149,8 @@ SUN_MAX_SAMPLES = 8
 SUN_MAX_MAPS = 8
 SUN_LISTS = 0
 SUN_ALL = 1
+SUN_BOUNCE_MAX_DIRS = 32
+SUN_MAX_BOUNCES = 8
 # fmgi_set_option (include/flatmatch_gi.h): tests' handles on product paths a scene would not take
 OPTIONS = {"chunk_items": 1, "pool_limit": 2, "stream_layout": 3, "bucket_fill": 4, "wide_tiles": 5, "coop": 6,
            "no_axes": 7, "photon_lock": 8, "lattice": 9, "hist_batch": 10}
@@ -516,6 +520,8 @@ def load() -> C.CDLL:
         "fmgi_sun_get_stats": (C.c_int, [vp, C.POINTER(SunStats)]),
         "fmgi_sun_add": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_double, vp, vp]),
         "fmgi_sun_units": (C.c_int, [vp, vp, vp, C.c_double, vp]),
+        "fmgi_rad_cache_sun_bounce": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
+        "fmgi_sun_add_bounced": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]),
         "fmgi_grid_copy": (C.c_int, [vp, vp, vp, vp, vp]),
         "fmgi_lattice_copy": (C.c_int, [vp, vp]),
         "fmgi_plan_copy": (C.c_int, [vp, vp, vp]),

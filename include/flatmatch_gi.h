@@ -685,7 +685,8 @@ int fmgi_filter_apply(fmgi_context *ctx, const void *radii_dev, const void *cons
                   lm_fx[t][c] += (cover[t] * unit[w][c] + S*S/2) / (S*S) in integers; lm_fx[t][3] is not touched.
                   After fmgi_finalize and main.c:68-79's normalisation with the same numSamplesPerArea a fully lit
                   texel gains 0.35 * rgb[c] * c_w.
-   Out of scope: the sun's bounced light, a penumbra, sun entering other than through a window rectangle.
+   Out of scope: a penumbra, sun entering other than through a window rectangle. The sun's bounced light is the
+   next section's.
 
    All calls use the scene of fmgi_set_scene (walls and windows). fmgi_sun_coverage and fmgi_sun_add are
    asynchronous on `stream`; to_sun and rgb are read before the call returns. FMGI_SUN_ALL tests every wall with
@@ -716,6 +717,58 @@ int fmgi_sun_add(fmgi_context *ctx, const void *cover_dev, const float to_sun[3]
                  void *const *lm_fx_dev, void *stream);
 /* host only, works on FMGI_HOST_ONLY contexts: units[numWalls][3], zero rows for walls that do not face */
 int fmgi_sun_units(fmgi_context *ctx, const float to_sun[3], const float rgb[3], double flux, int64_t *units);
+
+/* ---- Bounced sunlight: coverage maps gathered through the radiosity cache ------------ */
+/* fmgi_sun_add's light stops where it lands. A radiosity cache (above) holds, for every level-0 wall texel (a job),
+   the texel each of its 10000 cosine-distributed rays hits, whatever the lighting. A coverage map is a byte per
+   texel and a wall's cosine a constant, so the sun's radiosity on a texel is rgb x e[t] with a scalar e, and with one
+   reflectance per channel bounce n is rgb[c] x refl[c]^n x g_n[t]: g_n depends on the geometry and the sun's
+   direction only. fmgi_rad_cache_sun_bounce computes g_1 .. g_N per direction; fmgi_sun_add_bounced adds them under
+   any colour and reflectance to the int64 lightmap. No reference counterpart; the semantics below are the interface.
+
+   fp32 arithmetic is IEEE without contraction, in the order written; s, c_w and dot are the previous section's.
+     Start table  for direction k with coverage map cover_k made with S_k samples per texel edge, and a level-0 texel
+                  t of a wall w with c_w > 0: e_0[t] = ((float)cover_k[t] * c_w) / (float)(S_k*S_k). Every other entry
+                  of the cache's texel table is +0: walls that do not face the sun, mip levels, the window and light
+                  texels behind numTexels. A byte above S*S is used as it is (the caller's error, no memory hazard).
+                  c_w comes from the cache's own wall rectangles: bit for bit fmgi_sun_units' cosine.
+     Gather       for n = 1..N and job j with texel t_j: sum = +0; for ray r = 0..9999 in order, id = sids[j][r], if
+                  0 <= id < numTexels then sum = sum + e_{n-1}[id]; g_n[t_j] = sum / 10000.0f. g_n is +0 at every
+                  texel that is no job's, and e_n = g_n. Rays that miss (-1) and rays that hit a window or a light add
+                  nothing. There is no mip step and no 0.7 / 0.3 update: a Neumann series, not the reference's
+                  iteration.
+     Output       per direction a device float [N][numTexels] holding rows g_1 .. g_N; the call writes all of it. A
+                  direction's result depends neither on the other directions of the call nor on their number.
+     Adding       for map m with rgb_m[3] and refl_m[3], a level-0 texel t of wall w (every wall, facing or not) and
+                  channel c, in doubles: p_1 = (double)refl[c], p_n = p_{n-1} * (double)refl[c]; v = 0, then
+                  v = v + (double)g_n[t] * p_n for n = 1..N in order;
+                  q = (int64)floor(ldexp((((double)rgb[c] * v) * flux) * area_t, 25)) with the previous section's
+                  area_t; lm_fx[t][c] += q. Word 3 and the mip texels are not touched; a texel whose N values are all
+                  zero is not written. flux is the bake's numSamplesPerArea, as in fmgi_sun_add.
+
+   fmgi_rad_cache_sun_bounce draws nothing from libc. It is asynchronous on `stream`, like fmgi_rad_cache_solve: the
+   host arrays are read before it returns; its scratch belongs to the handle and is guarded by the handle's event (a
+   later call's stream waits, the host does not, unless the scratch has to grow); more than
+   FMGI_SUN_BOUNCE_MAX_DIRS directions run in further passes. Errors, found on the host before any device call:
+   FMGI_ERR_ARG for a NULL handle or pointer, num_dirs < 1, bounces outside 1..FMGI_SUN_MAX_BOUNCES, a samples[k]
+   outside 1..FMGI_SUN_MAX_SAMPLES, a to_sun of zero or non-finite length; then FMGI_ERR_NO_DEVICE.
+
+   fmgi_sun_add_bounced uses the context's scene, as fmgi_sun_add does; it is asynchronous, carries up to
+   FMGI_SUN_MAX_MAPS maps per pass and takes any number. Errors, in the previous section's order: FMGI_ERR_ARG for a
+   NULL context or pointer, bounces out of range, num_maps < 1, an rgb component outside [0, 32) or not finite, a refl
+   component outside [0, 1] or not finite, a flux not finite or <= 0; FMGI_ERR_STATE without a scene; FMGI_ERR_ARG if
+   32 * bounces * 1.001 * flux * max area_t * 2^25 reaches 2^55 (g_n <= 1 up to rounding, since e_0 <= 1 and a gather
+   averages: no deposit then reaches 2^55); FMGI_ERR_NO_DEVICE on a host-only context.
+   Out of scope: per-wall reflectance, the floor's tint and mirror, sky or lamp light through this path. */
+#define FMGI_SUN_BOUNCE_MAX_DIRS 32     /* directions one gather pass carries; the call takes any number */
+#define FMGI_SUN_MAX_BOUNCES 8
+int fmgi_rad_cache_sun_bounce(const fmgi_rad_cache *rc, void *const *cover_dev /* [num_dirs] uint8 [numTexels] */,
+                              const float *to_sun /* [num_dirs][3] */, const int *samples /* [num_dirs] */,
+                              int num_dirs, int bounces, void *const *bounce_dev /* [num_dirs] float [bounces][numTexels] */,
+                              void *stream);
+int fmgi_sun_add_bounced(fmgi_context *ctx, const void *bounce_dev, int bounces,
+                         const float *rgb /* [num_maps][3] */, const float *refl /* [num_maps][3] */, int num_maps,
+                         double flux, void *const *lm_fx_dev, void *stream);
 
 /* The kernel FMGI_KERNEL_AUTO resolves to for the current scene. */
 int fmgi_auto_kernel(const fmgi_context *ctx);

@@ -27,6 +27,13 @@ added to that scenario's lightmap after the filter and before it is finalised: -
 texel, one coverage map per distinct direction of the file, the flux the bake's --spa. It needs no photons and is
 the same on the dense, --sparse and --load-bake routes.
 
+--sun-bounces N (default 0) adds the sun's bounced light as well: the geometry's radiosity form factors
+are traced once (fmgi.RadCache, from the process's libc rand() position), every distinct direction's coverage map is
+gathered through them N times, 32 directions to a pass, and each scenario's bounced layer is added right after its
+direct sun. --sun-reflectance R G B is the walls' reflectance per channel, one for every wall; its default 0.9 is the
+bake's diffuse factor (photonmap.cl:249). The floor's tint and mirror are not modelled. With N = 0 none of this runs and
+the files are the bytes they were.
+
 A bake of few photons is speckled; --min-deposits N smooths every scenario's lightmap with the adaptive density
 filter before it is finalised: per texel a window of radius <= --max-radius, grown until it
 holds the energy of N first-bounce window photons in the reference-palette lightmap of all groups, so all
@@ -206,6 +213,12 @@ def parse_args(argv=None):
     ap.add_argument("--max-radius", type=int, default=4, help="the filter's largest window radius in texels (0..16)")
     ap.add_argument("--sun-samples", type=int, default=4,
                     help="scenarios with a sun: N x N shadow rays per texel (1..8, default 4)")
+    ap.add_argument("--sun-bounces", type=int, default=0,
+                    help="scenarios with a sun: bounces of its light through the radiosity form factors (0..8, default "
+                         "0: direct sun only)")
+    ap.add_argument("--sun-reflectance", type=float, nargs=3, default=[0.9, 0.9, 0.9], metavar=("R", "G", "B"),
+                    help="--sun-bounces: the walls' reflectance per channel in [0, 1] (default 0.9, the bake's diffuse "
+                         "factor)")
     ap.add_argument("--sparse", action="store_true",
                     help="compact every group's histogram into its sparse form and recolour from the blobs")
     ap.add_argument("--save-bake", default=None, metavar="FILE", help="write the traced scene to FILE (implies --sparse)")
@@ -230,6 +243,10 @@ def parse_args(argv=None):
         ap.error("--max-radius must be in 0..16")
     if not 1 <= a.sun_samples <= 8:
         ap.error("--sun-samples must be in 1..8")
+    if not 0 <= a.sun_bounces <= 8:
+        ap.error("--sun-bounces must be in 0..8")
+    if not all(np.isfinite(v) and 0.0 <= v <= 1.0 for v in a.sun_reflectance):
+        ap.error("--sun-reflectance must be three numbers in [0, 1]")
     return a
 
 
@@ -332,12 +349,26 @@ def main(argv=None):
         for k, sun in enumerate(suns):
             if sun is not None:
                 by_dir.setdefault(sun[0].tobytes(), []).append(k)
+        covers = []
         for ks in by_dir.values():
             to_sun = suns[ks[0]][0]
             cover = torch.empty(max(T, 1), dtype=torch.uint8, device=dev)
             ctx.sun_coverage(to_sun, a.sun_samples, cover.data_ptr(), stream=s.cuda_stream)
-            ctx.sun_add(cover.data_ptr(), to_sun, a.sun_samples, [suns[k][1] for k in ks], a.spa,
-                        [lms[k].data_ptr() for k in ks], s.cuda_stream)
+            covers.append(cover)
+        bounced = None
+        if a.sun_bounces > 0 and by_dir:
+            # the sun's bounced light: the form factors once, every direction's tables in one call
+            if int(os.environ.get("FMGI_DEVICE", 0)) != a.device:
+                sys.exit(f"--sun-bounces: the form factors are traced on device FMGI_DEVICE, not on --device {a.device}")
+            rad = fmgi.RadCache(sc)
+            bounced = rad.sun_bounce(covers, [suns[ks[0]][0] for ks in by_dir.values()], a.sun_samples, a.sun_bounces,
+                                     stream=s.cuda_stream)
+        for d, (ks, cover) in enumerate(zip(by_dir.values(), covers)):
+            to_sun, ptrs = suns[ks[0]][0], [lms[k].data_ptr() for k in ks]
+            ctx.sun_add(cover.data_ptr(), to_sun, a.sun_samples, [suns[k][1] for k in ks], a.spa, ptrs, s.cuda_stream)
+            if bounced is not None:
+                ctx.sun_add_bounced(bounced[d].data_ptr(), a.sun_bounces, [suns[k][1] for k in ks],
+                                    [a.sun_reflectance] * len(ks), a.spa, ptrs, s.cuda_stream)
         zero = torch.zeros((T, 4), dtype=torch.float32, device=dev)
         texels = [torch.empty((T, 4), dtype=torch.float32, device=dev) for _ in entries]
         for lm, t in zip(lms, texels):
@@ -365,6 +396,11 @@ def main(argv=None):
     if by_dir:
         print(f"  sun: {len(by_dir)} direction{'s' if len(by_dir) > 1 else ''}, {a.sun_samples} x {a.sun_samples} "
               f"rays per texel, {sum(len(ks) for ks in by_dir.values())} scenarios")
+    if bounced is not None:
+        info = rad.info
+        print(f"  sun bounces: {a.sun_bounces} through {info['jobs']} jobs' form factors ({info['rays']} rays traced in "
+              f"{info['rand_ms'] + info['rays_ms']:.1f} ms), reflectance {' '.join(f'{v:g}' for v in a.sun_reflectance)}")
+        rad.close()
     if a.min_deposits > 0:
         print(f"  filtered: {a.min_deposits} deposits, radius <= {a.max_radius}, mean radius "
               f"{radii.float().mean().item():.3f}")
